@@ -12,7 +12,9 @@ overlapped with backward] -> fused AdamW.  Workload = BASELINE.json configs[1]/[
 clip (480 000 samples, 0.1*N(0,1), seed 1234+idx) and S=1024 tokens (9 prompt + 750 <sound> + 9 prompt + 256 answer, loss on
 the answer), micro-batch 8 per GPU, random-init weights N(0, 0.02) of the AF3-7B architecture.
 
-Rank 0 prints ONE JSON line.  value = audio-seconds/s over all ranks; decoder tokens/s are reported beside it.
+Rank 0 prints ONE JSON line.  value = audio-seconds/s over all ranks; decoder tokens/s are reported beside it.  A plain run does only that: set up,
+warm up, time --steps steps, [--dump-outputs DIR: the last timed step's outputs as .npy], print the line.  --full adds every other measurement
+(roofline steps, checksums, long-audio / decode / ICL / parity legs, eager-ROCm and CPU baselines, the detail record).
 """
 import argparse
 import json
@@ -495,6 +497,24 @@ def write_detail(res, name="bench_detail.json"):
         return None
 
 
+DUMP_SAMPLE = 1 << 21   # elements per sampled array of dump_outputs: 8 MiB each in float32, ~40 MiB for the whole dump
+
+
+def dump_outputs(out_dir, loss, arena):
+    """what the last timed step hands its caller, as float32 .npy files under out_dir (for output-for-output comparison of two builds):
+    loss.npy (its loss), and at DUMP_SAMPLE fixed positions of the flat arenas - drawn from a seeded generator, sorted, the same in every run of the
+    same configuration - params_sample.npy (the bf16 parameters its AdamW left), grads_sample.npy (the bf16 gradients its backward left) and
+    sample_index.npy (the positions, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    idx = torch.randint(0, arena.total, (min(DUMP_SAMPLE, arena.total),), generator=torch.Generator().manual_seed(0)).sort().values
+    idx_dev = idx.to(arena.params.device)
+    arrays = {"loss": loss.detach().float().reshape(1).cpu(), "params_sample": arena.params.index_select(0, idx_dev).float().cpu(),
+              "grads_sample": arena.grads.index_select(0, idx_dev).float().cpu(), "sample_index": idx.double()}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
 def mfma_power_ceiling(dev, seconds=1.2):
     """what the matrix pipe sustains on THIS chip under its power cap when nothing but MFMAs run (csrc/ceiling.hip mode 0: v_mfma_f32_32x32x16_bf16 on
     N(0,1) operands resident in registers, 256 workgroups x 8 waves, no LDS / global access in the loop): 0.3 s ramp + `seconds` timed with HIP events.
@@ -685,6 +705,11 @@ def main():
                     "stdout line is the <= 4 KB summary of it")
     ap.add_argument("--dry-run-cpu", action="store_true", help="CONTROL-FLOW TEST ONLY (tests/test_host_cpu.py): no GPU, no kernels - the N > 1 sequence of this script "
                     "(process group, parameter broadcast, per-bucket exchange in backward order, replica checksum, one JSON line on rank 0) with a stub in place of the step")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: per-GEMM HIP events in the timed steps, the host-enqueue and serial "
+                    "roofline steps, parameter checksums / replica check, the long-audio, decode, ICL, power-ceiling and full-depth parity legs, the eager-ROCm and CPU "
+                    "baselines, and the detail record (--detail-name).  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last one computed to DIR/<name>.npy: "
+                    "its loss and a fixed, seeded sample of the parameters and gradients it left, in float32 (dump_outputs)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_spawn(args.gpus)
@@ -711,7 +736,8 @@ def main():
     local_rank %= max(torch.cuda.device_count(), 1)  # --backend gloo: several ranks may share one GPU (control-flow tests on 1-GPU boxes)
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
-    waited = 0.0 if args.no_settle else settle_hbm(dev)
+    # a plain run spends at most 30 s outside its steps: its wait is bounded at 15 s (~7 s of VRAM release + the 8 s quiet window after a previous replica)
+    waited = 0.0 if args.no_settle else settle_hbm(dev, timeout_s=60.0 if args.full else 15.0)
     if args.parity_fulldepth:
         from tools import parity_fulldepth as _pf
 
@@ -924,7 +950,7 @@ def main():
         configure_dp(bk, bf)   # fresh optimizer state for the chosen form (the probe's steps trained the replicas like any other step)
     elif use_dp:
         dp_info["chosen"] = f"{cands[0][0]}:{cands[0][1]}"
-    if overlap is not None and not use_graph and use_dp:
+    if overlap is not None and not use_graph and use_dp and args.full:
         overlap.measure_tail = True
     run = step
     if use_graph:
@@ -936,8 +962,9 @@ def main():
         load_next()
         loss = run()
     fence()
-    ops.prof_reset()
-    ops.prof_enable(True)
+    if args.full:
+        ops.prof_reset()
+        ops.prof_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         load_next()
@@ -945,6 +972,8 @@ def main():
     host_enqueue = time.perf_counter() - t0  # host time to enqueue the steps (no sync inside; includes queue back-pressure once the GPU lags)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model.arena)
     if overlap is not None and overlap.measure_tail:
         tail = overlap.exposed_tail_ms(last=args.steps)   # compute stream idle behind the last backward kernel: [exchange ->] AdamW -> shadows of the last buckets
         if use_dp:
@@ -953,20 +982,24 @@ def main():
             tail = float(tt.item())
         dp_info["exposed_comm_ms"] = None if tail is None else round(tail, 2)
         overlap.measure_tail = False
-    # the same WITHOUT back-pressure: one more (untimed) step enqueued onto an idle GPU - what the host really needs per step
-    t1 = time.perf_counter()
-    load_next()
-    loss = run()
-    host_enqueue_idle = time.perf_counter() - t1
-    fence()
-    ops.prof_enable(False)
-    ov_ms, ov_flops, ov_launches = ops.prof_collect()
+    host_enqueue_idle = None
+    if args.full:
+        # the same WITHOUT back-pressure: one more (untimed) step enqueued onto an idle GPU - what the host really needs per step
+        t1 = time.perf_counter()
+        load_next()
+        loss = run()
+        host_enqueue_idle = time.perf_counter() - t1
+        fence()
+        ops.prof_enable(False)
+        ov_ms, ov_flops, ov_launches = ops.prof_collect()
     # Per-launch GEMM durations: with the wgrad branch on a second stream and AdamW on a third, kernels share the chip and the
     # HIP-event brackets of the timed region over-state each launch.  One extra UNTIMED step on the serial schedule (one stream,
     # optimizer after backward) gives the same launches back to back; that is what `roofline.achieved` is computed from (both are
     # reported; profiles/r01f_bench_kernel_stats_serial.md is the rocprofv3 view of the same schedule).
     had_side = model.arena.wgrad_stream is not None
-    if had_side:
+    if not args.full:
+        adamw_ms = None
+    elif had_side:
         model.arena.join_streams()
         model.arena.enable_wgrad_stream(False)
         fence()
@@ -994,6 +1027,7 @@ def main():
         t = torch.tensor([dt], device=coll_dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if use_dp and args.full:
         # every replica must hold bit-identical parameters after the timed steps (same reduced gradients, same AdamW): checksum per rank
         model.arena.join_streams()
         p32 = model.arena.params.float()
@@ -1006,16 +1040,18 @@ def main():
         del p32
     peak_mem = torch.cuda.max_memory_allocated(dev) / 2 ** 30
 
-    # parameter checksum of this replica after the timed steps (every run prints it: two schedules of the same code - eager / HIP graph, with /
+    # parameter checksum of this replica after the timed steps (every --full run prints it: two schedules of the same code - eager / HIP graph, with /
     # without the RCCL path - must agree on it bit for bit, tests/test_dp_gpu.py)
-    model.arena.join_streams()
-    torch.cuda.synchronize()
-    _p32 = model.arena.params.float()
-    param_checksum = [float(_p32.sum().double()), float(_p32.abs().sum().double())]
-    del _p32
+    param_checksum = None
+    if args.full:
+        model.arena.join_streams()
+        torch.cuda.synchronize()
+        _p32 = model.arena.params.float()
+        param_checksum = [float(_p32.sum().double()), float(_p32.abs().sum().double())]
+        del _p32
 
-    # BASELINE configs[4] (long audio) beside the headline: a few steps of the 5-minute workload on the same replica, so that the
-    # driver's plain `bench.py --gpus N` run records it too (one sample = 10 windows, S = 7 774, per-layer activation checkpointing);
+    # BASELINE configs[4] (long audio) beside the headline: a few steps of the 5-minute workload on the same replica, so that a
+    # `bench.py --full` run records it too (one sample = 10 windows, S = 7 774, per-layer activation checkpointing);
     # then the same at AF3's stated maximum clip length (10 minutes = 20 windows, S = 15 274; /root/reference README.md:109)
     def long_leg(name, label):
         """both recompute plans of the long-audio workloads: "reference" = every layer recomputed, what
@@ -1100,7 +1136,7 @@ def main():
         print(f"[bench] cu_contention (ms/step beside n parked CUs): {cu_contention}", file=sys.stderr, flush=True)
 
     long_audio = long_10min = None
-    if args.workload == "clip30" and full_model and not args.no_long_audio:
+    if args.full and args.workload == "clip30" and full_model and not args.no_long_audio:
         long_audio = long_leg("long5min", "5-min clips (BASELINE configs[4])")
         long_10min = long_leg("long10min", "10-min clips (AF3's stated maximum, /root/reference README.md:109)")
 
@@ -1108,7 +1144,7 @@ def main():
     # per-token time = (33 new tokens - 1 new token) / 32, i.e. the graph-replayed decode step incl. its one-time capture, against the
     # weight-streaming roofline (every decoder weight + lm_head read once per token: 15.2 GB bf16 at 8 TB/s)
     decode = None
-    if args.workload == "clip30" and full_model and not args.no_extra_legs and world == 1:
+    if args.full and args.workload == "clip30" and full_model and not args.no_extra_legs and world == 1:
         try:
             decode = decode_leg(model, frontend, waves, ids, dev)
         except Exception as e:
@@ -1117,26 +1153,28 @@ def main():
     if rank == 0:
         ms_per_step = 1000.0 * dt / args.steps
         samples_per_s = world * args.batch * args.steps / dt
-        achieved_tf = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        # roofline.traffic: PMC passes cannot run inside bench.py, so the committed rocprofv3 --pmc result (tools/measure_gemm_traffic.py) is
-        # quoted - but ONLY when it was measured on THIS build of the kernels (afk_build_id stamp); a figure from other sources is refused
-        import glob
+        achieved_tf = gemm_flops / (gemm_ms * 1e-3) / 1e12 if args.full and gemm_ms > 0 else 0.0
+        traffic = traffic_detail = None
+        if args.full:
+            # roofline.traffic: PMC passes cannot run inside bench.py, so the committed rocprofv3 --pmc result (tools/measure_gemm_traffic.py) is
+            # quoted - but ONLY when it was measured on THIS build of the kernels (afk_build_id stamp); a figure from other sources is refused
+            import glob
 
-        from audio_flamingo_amd import _lib as _afk_lib
+            from audio_flamingo_amd import _lib as _afk_lib
 
-        build_id = _afk_lib.load().afk_build_id().decode()
-        traffic, traffic_detail = None, {"this_build": build_id, "note": "no PMC measurement of this build under profiles/ (python tools/measure_gemm_traffic.py)"}
-        for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_gemm_traffic*.json")), reverse=True):
-            with open(tpath) as f:
-                tj = json.load(f)
-            if tj.get("afk_build_id") == build_id:
-                traffic = tj["hbm_bytes_per_launch"]  # HBM bytes of ONE launch of the kernel on the shape below (largest GEMM of the step)
-                traffic_detail = {"hbm_bytes_per_launch": tj["hbm_bytes_per_launch"], "algorithmic_bytes_per_launch": tj["algorithmic_bytes_per_launch"],
-                                  "shape": tj["shape"], "afk_build_id": build_id, "l2_hit_rate": tj.get("l2_hit_rate"),
-                                  "source": os.path.relpath(tpath, ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes; stamped with the build it ran on)"}
-                break
-            traffic_detail.setdefault("stale", []).append({"file": os.path.relpath(tpath, ROOT), "measured_on_build": tj.get("afk_build_id", "unstamped (round 2)"),
-                                                            "hbm_bytes_per_launch": tj.get("hbm_bytes_per_launch")})
+            build_id = _afk_lib.load().afk_build_id().decode()
+            traffic_detail = {"this_build": build_id, "note": "no PMC measurement of this build under profiles/ (python tools/measure_gemm_traffic.py)"}
+            for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_gemm_traffic*.json")), reverse=True):
+                with open(tpath) as f:
+                    tj = json.load(f)
+                if tj.get("afk_build_id") == build_id:
+                    traffic = tj["hbm_bytes_per_launch"]  # HBM bytes of ONE launch of the kernel on the shape below (largest GEMM of the step)
+                    traffic_detail = {"hbm_bytes_per_launch": tj["hbm_bytes_per_launch"], "algorithmic_bytes_per_launch": tj["algorithmic_bytes_per_launch"],
+                                      "shape": tj["shape"], "afk_build_id": build_id, "l2_hit_rate": tj.get("l2_hit_rate"),
+                                      "source": os.path.relpath(tpath, ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes; stamped with the build it ran on)"}
+                    break
+                traffic_detail.setdefault("stale", []).append({"file": os.path.relpath(tpath, ROOT), "measured_on_build": tj.get("afk_build_id", "unstamped (round 2)"),
+                                                                "hbm_bytes_per_launch": tj.get("hbm_bytes_per_launch")})
         model_tf = train_flops_per_sample(s_tok, windows) * samples_per_s / world / 1e12 if full_model else None
         plan = {k: v for k, v in (model.ckpt_plan or {}).items() if not k.startswith("_")} if ckpt else None
         rc = (plan.get("enc", 32), plan.get("dec", 28)) if plan else bool(ckpt)     # layers the memory-budgeted plan really recomputed
@@ -1182,7 +1220,7 @@ def main():
                                                },
             "long_audio_configs4": long_audio, "long_audio_10min": long_10min, "decode": decode, "cu_contention_ms_per_step": cu_contention,
             "peak_mem_gib": round(peak_mem, 1), "host_enqueue_ms_per_step": round(1000.0 * host_enqueue / args.steps, 1),
-            "host_enqueue_ms_idle_gpu": round(1000.0 * host_enqueue_idle, 1),
+            "host_enqueue_ms_idle_gpu": None if host_enqueue_idle is None else round(1000.0 * host_enqueue_idle, 1),
             "waited_for_free_hbm_s": waited,
             "model_tflops_per_gpu": model_tf, "model_frac_of_mfma_peak": (model_tf / 2500.0) if model_tf else None,
             "hardware_tflops_per_gpu": hw_tf, "executed_tflops_per_gpu": exec_tf,
@@ -1193,7 +1231,7 @@ def main():
                 "note": "HIP events around the full-width AdamW launches of the extra serial step (alone on the chip); 6.29 TB/s is the achievable streaming rate (MI355X_MICROARCH.md)"},
             "lm_head_rows": {"executed": N_ANSWER, "of": s_tok, "note": "lm_head/CE and their backward GEMMs run on the labelled rows only (same loss, same gradients)",
                              "last_decoder_layer_behind_its_attention": bool(getattr(model, "last_layer_rows_only", False))},
-            "roofline": {"bound": "mfma", "kernel": "gemm_nt_bf16_k256 (+ k128 for <192-tile shapes): every dense contraction (fwd, dgrad, wgrad, conv stem, lm_head)",
+            "roofline": None if not args.full else {"bound": "mfma", "kernel": "gemm_nt_bf16_k256 (+ k128 for <192-tile shapes): every dense contraction (fwd, dgrad, wgrad, conv stem, lm_head)",
                          "achieved": achieved_tf, "peak": 2500.0, "unit": "TFLOP/s", "frac": achieved_tf / 2500.0, "traffic": traffic, "traffic_detail": traffic_detail,
                          "launches": gemm_launches, "avg_launch_ms": gemm_ms / max(gemm_launches, 1),
                          "gemm_ms_per_step": gemm_ms / prof_steps,
@@ -1211,7 +1249,7 @@ def main():
                                   "disabled (launches back to back)" if had_side else "HIP events around every GEMM launch, timed region")
                                  + "; the gate|up launches carry the fused SwiGLU forward: its elementwise work counts as GEMM time, not as flops"},
         }
-        if world == 1 and full_model and not args.no_extra_legs:
+        if args.full and world == 1 and full_model and not args.no_extra_legs:
             # the measured ceiling the GEMM is held against: pure-MFMA rate of this chip under its power cap, live, beside `frac`
             try:
                 ceil_tf = mfma_power_ceiling(dev)
@@ -1219,9 +1257,9 @@ def main():
                 res["roofline"]["frac_of_power_ceiling"] = achieved_tf / ceil_tf
             except Exception as e:
                 res["roofline"]["power_ceiling_error"] = repr(e)[:200]
-        want_eager = not args.no_eager_baseline and world == 1 and args.workload == "clip30"
-        want_icl = not args.no_extra_legs and world == 1 and args.workload == "clip30" and full_model
-        want_parity = not args.no_parity and world == 1 and args.workload == "clip30" and full_model and args.batch == 8
+        want_eager = args.full and not args.no_eager_baseline and world == 1 and args.workload == "clip30"
+        want_icl = args.full and not args.no_extra_legs and world == 1 and args.workload == "clip30" and full_model
+        want_parity = args.full and not args.no_parity and world == 1 and args.workload == "clip30" and full_model and args.batch == 8
         if want_eager or want_icl or want_parity:
             # both need the HBM of our replica (the ICL model: 4.3 B parameters + fp32 AdamW state; the reference model: 125 GiB): free it first
             feats_b = frontend(waves, out_dtype=torch.bfloat16)
@@ -1274,7 +1312,7 @@ def main():
                     res["speedup_vs_eager_rocm"] = res["value"] / eb["value"]
             except Exception as e:
                 res["eager_rocm_baseline"] = {"value": None, "unit": "audio-s/s", "error": repr(e)[:300]}
-        if not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N = 1 only
             try:
                 res["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # the baseline must never take the measured line down
@@ -1282,7 +1320,7 @@ def main():
         # hardware = executed (what the kernels really did, recompute included, unlabelled lm_head rows excluded); the algorithmic figure stays `model_*`
         res["hardware_tflops_per_gpu"] = res["executed_tflops_per_gpu"]
         res["executed_frac_of_mfma_peak"] = (res["executed_tflops_per_gpu"] / 2500.0) if res["executed_tflops_per_gpu"] else None
-        line = compact_line(res, write_detail(res, args.detail_name))
+        line = compact_line(res, write_detail(res, args.detail_name) if args.full else None)
     else:
         line = None
     def drain():

@@ -289,7 +289,7 @@ def test_native_comm_single_rank(dev):
 
 # ------------------------------------------------------------------------------------------------ bench.py's own multi-rank paths
 _BENCH_TINY = ["--enc-layers", "1", "--dec-layers", "1", "--batch", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-eager-baseline",
-               "--no-long-audio", "--no-extra-legs", "--no-settle"]
+               "--no-long-audio", "--no-extra-legs", "--no-settle", "--full"]   # --full: the parameter checksum and the detail record compared below
 
 
 class BenchAborted(Exception):
@@ -385,3 +385,34 @@ def test_bench_two_ranks_on_one_gpu_gloo(dev):
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["replicas_identical_after_steps"] is True and d["dp"]["backend"] == "gloo", d
     assert len(d["rank_losses"]) == 2 and d["rank_losses"][0] != d["rank_losses"][1], d["rank_losses"]   # the ranks trained on different samples
     assert d["config"]["global_batch"] == 4 and d["step_enqueue"] == "eager_python"
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(dev, tmp_path):
+    """--dump-outputs DIR on a plain run (no --full): float32 / float64 arrays of the LAST timed step - its loss (the line's), a seeded sample of the
+    parameters and gradients - under 64 MB in all; the same arguments dump bit-identical arrays, and --steps sets how many steps trained"""
+    import json
+
+    import numpy as np
+
+    def run(steps, out):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(out),
+               "--enc-layers", "1", "--dec-layers", "1", "--batch", "2", "--no-settle"]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, (cmd, r.stdout[-3000:], r.stderr[-3000:])
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        files = sorted(out.iterdir())
+        assert [f.name for f in files] == ["grads_sample.npy", "loss.npy", "params_sample.npy", "sample_index.npy"], files
+        assert sum(f.stat().st_size for f in files) < 64 << 20
+        arrays = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        return line, arrays
+
+    line, a = run(3, tmp_path / "a")
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and "detail" not in line and "roofline" not in line, line
+    assert abs(float(a["loss"][0]) - line["loss"]) < 1e-3 and np.isfinite(a["loss"]).all()
+    assert a["params_sample"].shape == a["grads_sample"].shape == a["sample_index"].shape and np.abs(a["grads_sample"]).max() > 0
+    _, b = run(3, tmp_path / "b")
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    line2, c = run(2, tmp_path / "c")
+    assert line2["steps"] == 2 and np.array_equal(c["sample_index"], a["sample_index"]) and not np.array_equal(c["params_sample"], a["params_sample"])
