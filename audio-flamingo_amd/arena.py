@@ -39,6 +39,7 @@ class Block:
     data: Optional[torch.Tensor] = None
     grad: Optional[torch.Tensor] = None
     fresh: bool = True  # no gradient written since the last zero_grad -> next wgrad overwrites instead of accumulating
+    pending: int = 0    # writes announced by forwards (Arena.expect_writes) that have not landed yet
     shadow: Optional[torch.Tensor] = None
     shadow_kind: Optional[str] = None  # "T" (W^T), "conv" (tap-major + its transpose)
     shadow_aux: Optional[torch.Tensor] = None
@@ -57,8 +58,19 @@ class Arena:
         self.total = 0
         self.step_counter = 0  # bumped by our optimizer (raw-pointer writes do not touch tensor._version)
         self._bucket_ranges: List[tuple] = []
+        # writes each bucket still expects before it is complete (on_bucket_ready fires when this reaches 0).  The stages' forwards announce their
+        # backward's writes (expect_writes): two forwards of a layer in one backward, or two heads on one weight, double that layer's count.  Until a
+        # forward has announced anything since zero_grad() the count is the bucket's static block count (one write per block: hosts that drive
+        # grad_written() themselves)
         self._bucket_pending: List[int] = []
-        self.presums = {}   # one hand-over slot {for: bias key, ptr: data_ptr of the gradient tensor, row: bf16 column sums}: left by a gradient's producer for the bias gradient of its consumer (functional.py)
+        self._announced = False
+        # one hand-over slot {for: bias key, dx: the gradient tensor (held), version: its _version, row: bf16 column sums}: left by a gradient's
+        # producer for the bias gradient of its consumer (functional.py).  Keyed on the tensor OBJECT and its version, never its address: autograd
+        # may add a second consumer's gradient into that tensor in place, and the allocator hands a later tensor the same address
+        self.presums = {}
+        # lm_head + loss parks its unscaled weight gradient in the arena during the forward (functional.LMHeadLossFn): key -> None while it sits
+        # there, or the private copy it was moved to when another write to that block was announced before the parking stage's backward ran
+        self.parked: Dict[str, Optional[torch.Tensor]] = {}
         self._bucket_sizes: List[int] = []
         self.on_bucket_ready: Optional[Callable[[int], None]] = None
         # optional second compute stream for the weight-gradient branch of every Linear backward (functional.linear_bwd):
@@ -144,20 +156,43 @@ class Arena:
         (needed only for tensors that receive sparse updates, e.g. embed_tokens: handled by its Function)."""
         for b in self.order:
             b.fresh = True
+            b.pending = 0
         self._bucket_pending = list(self._bucket_sizes)
+        self._announced = False
+        self.presums.clear()
+        self.parked.clear()
         if memset:
             self.grads.zero_()
+
+    def expect_writes(self, blocks):
+        """a stage's forward (not its re-run under checkpointing) announces the gradient writes its backward will make: one per block listed.
+        A bucket is complete when every announced write has landed - not after as many writes as it has blocks"""
+        if not self._announced:
+            self._announced = True
+            self._bucket_pending = [0] * len(self._bucket_sizes)
+        for b in blocks:
+            self._bucket_pending[b.bucket] += 1
+            b.pending += 1
+            if b.key in self.parked and self.parked[b.key] is None:
+                # another write to a block whose unscaled gradient is parked in the arena: move it out before that write can land on it
+                self.parked[b.key] = b.grad.clone()
 
     def grad_written(self, blk: Block):
         """called by the wgrad sites after enqueueing the kernels that finish blk.grad for this backward"""
         if blk.fresh:
             blk.fresh = False
+        if blk.pending > 0:
+            blk.pending -= 1
         self._bucket_pending[blk.bucket] -= 1
         if self._bucket_pending[blk.bucket] == 0 and self.on_bucket_ready is not None:
             self.on_bucket_ready(blk.bucket)
 
     def begin_backward(self):
-        self._bucket_pending = list(self._bucket_sizes)
+        """start of a step's exchange (BackwardOverlap.begin_step / DataParallelEngine.begin_backward), before or after its forward.  Announced
+        writes still outstanding are kept (they belong to forwards whose backward has not run); without announcements every bucket expects one
+        write per block again"""
+        if not self._announced:
+            self._bucket_pending = list(self._bucket_sizes)
         self.presums.clear()
 
     def enable_wgrad_stream(self, on: bool = True):

@@ -47,6 +47,11 @@ BWD_FORM = os.environ.get("AFK_BWD_FORM", "wgrad_direct")
 DIRECT_MIN_TILES = 192
 
 
+def _prefixed(arena, pfx):
+    """keys of every arena block of one layer (its backward writes each exactly once)"""
+    return [b.key for b in arena.order if b.key.startswith(pfx)]
+
+
 def _tiles256(m, n):
     return ((m + 255) // 256) * ((n + 255) // 256)
 
@@ -183,6 +188,11 @@ def linear_bwd(arena: Arena, dy, x, wkey, *, bkey=None, bias_slices=None, need_d
 class ConvStemFn:
     """gelu(conv1) -> gelu(conv2, stride 2) -> permute -> + embed_positions   (modeling_audioflamingo3.py:380-385)"""
 
+    # grad_keys(arena, *static args): the arena blocks the stage's backward writes, once each (stage_ops announces them at forward time)
+    @staticmethod
+    def grad_keys(arena, keys, W, T, C):
+        return list(keys)
+
     @staticmethod
     def forward(ctx, feats, anchor, arena, keys, pos, W, T, C):
         k1w, k1b, k2w, k2b = keys
@@ -252,6 +262,10 @@ class EncoderLayerFn:
     """pre-LN attention block + pre-LN GELU MLP   (AudioFlamingo3EncoderLayer.forward, :211-245)"""
 
     @staticmethod
+    def grad_keys(arena, pfx, W, S, H):
+        return _prefixed(arena, pfx)
+
+    @staticmethod
     def forward(ctx, x, anchor, arena, pfx, W, S, H, kv_len):
         E = x.shape[1]
         D = E // H
@@ -278,15 +292,18 @@ class EncoderLayerFn:
         arena, pfx, W, S, H, D = ctx.meta
         E = x.shape[1]
         A = lambda k: arena[pfx + k]
+        fuse = FUSE_BIAS_SUMS and E % 8 == 0 and E <= 4096
+        # fc2's grad_output is the gradient this layer received: if it is the very tensor the layer above produced, unchanged since (same object, same
+        # version: autograd adds a second consumer's gradient in place, the allocator gives a later tensor the same address), that layer's LayerNorm
+        # backward has summed its columns already
+        slot = arena.presums
+        pre2 = None
+        if fuse and slot.get("for") == pfx + "fc2.bias" and slot.get("dx") is dx3 and dx3._version == slot.get("version"):
+            pre2 = slot["row"]
+        arena.presums.clear()   # one slot, consumed or dropped by the next layer down: nothing stale survives to a later backward
         dx3 = dx3.contiguous()
         if f is None:
             f = ops.gelu_fwd(pre)
-        fuse = FUSE_BIAS_SUMS and E % 8 == 0 and E <= 4096
-        # fc2's grad_output is the gradient this layer received: if the layer above produced it (same storage), its LayerNorm backward has summed its columns already
-        pre2 = None
-        if fuse and arena.presums.get("for") == pfx + "fc2.bias" and arena.presums.get("ptr") == dx3.data_ptr():
-            pre2 = arena.presums["row"]
-        arena.presums.clear()   # one slot, consumed or dropped by the next layer down: nothing stale survives to a later backward
         df = linear_bwd(arena, dx3, f, pfx + "fc2.weight", bkey=pfx + "fc2.bias", bias_presum=pre2)
         del f
         b1 = A("fc1.bias")
@@ -312,20 +329,26 @@ class EncoderLayerFn:
                         bias_slices=[(0, E), (2 * E, 3 * E)])
         del dqkv
         lw, lb = A("self_attn_layer_norm.weight"), A("self_attn_layer_norm.bias")
-        # the dx this layer hands down is the grad_output of the LOWER layer's fc2: its column sums go into a scratch row, registered under dx's storage - the
-        # lower layer takes them only if it receives exactly this tensor (anything else - another consumer of the hidden state, a copy - falls back to the column-sum pass)
+        # the dx this layer hands down is the grad_output of the LOWER layer's fc2: its column sums go into a scratch row, registered under the dx tensor itself
+        # (held, so that the identity check cannot meet a new tensor in its place) and its version - the lower layer takes them only if it receives exactly this
+        # tensor, unmodified (anything else - another consumer's gradient added into it, a copy - falls back to the column-sum pass).  zero_grad() and every
+        # forward clear the slot
         lower = _lower_fc2_bias(arena, pfx) if fuse else None
         row = torch.empty(E, device=x.device, dtype=torch.bfloat16) if lower else None
         dx = ops.layernorm_bwd(x, lw.data, dh, mean1, rstd1, lw.grad, lb.grad, dx_add=dx2, accumulate=not lw.fresh, colsum_out=row, colsum_accumulate=False)
         arena.grad_written(lw), arena.grad_written(lb)
         if row is not None:
-            arena.presums.update({"for": lower, "ptr": dx.data_ptr(), "row": row})
+            arena.presums.update({"for": lower, "dx": dx, "version": dx._version, "row": row})
         return dx, None, None, None, None, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------- avg-pool + LN (a7)
 class PoolNormFn:
     """AvgPool1d(2,2) over time then LayerNorm (:401-403)"""
+
+    @staticmethod
+    def grad_keys(arena, wkey, bkey, out_rows):
+        return [wkey, bkey]
 
     @staticmethod
     def forward(ctx, x, anchor, arena, wkey, bkey, out_rows):
@@ -365,6 +388,10 @@ class ProjectorFn:
     """Linear -> GELU -> Linear (AudioFlamingo3MultiModalProjector.forward, :435-439)"""
 
     @staticmethod
+    def grad_keys(arena, pfx):
+        return _prefixed(arena, pfx)
+
+    @staticmethod
     def forward(ctx, x, anchor, arena, pfx):
         A = lambda k: arena[pfx + k]
         pre = torch.empty((x.shape[0], A("linear_1.weight").shape[0]), device=x.device, dtype=torch.bfloat16)
@@ -392,6 +419,10 @@ class EmbedScatterFn:
     """embed_tokens(input_ids) with <sound> rows overwritten by audio rows in row-major order (:532-545)"""
 
     @staticmethod
+    def grad_keys(arena, ekey):
+        return [ekey]
+
+    @staticmethod
     def forward(ctx, audio, anchor, arena, ekey, ids, src):
         out = ops.embed_scatter_fwd(ids, src, arena[ekey].data, audio)
         ctx.save_for_backward(ids, src)
@@ -417,6 +448,10 @@ class EmbedScatterFn:
 # ---------------------------------------------------------------------------------------------- decoder layer (a13-a16)
 class DecoderLayerFn:
     """RMSNorm -> GQA causal attention (RoPE) -> +res ; RMSNorm -> SwiGLU -> +res  (Qwen2DecoderLayer.forward, :269-298)"""
+
+    @staticmethod
+    def grad_keys(arena, pfx, B, S, Hq, Hkv, D, eps):
+        return _prefixed(arena, pfx)
 
     @staticmethod
     def forward(ctx, x, anchor, arena, pfx, B, S, Hq, Hkv, D, eps, cos, sin, pos, kv_len, krange=None, kv_lo=None, rows=None):
@@ -499,6 +534,10 @@ class RMSNormFn:
     """final Qwen2RMSNorm (modeling_qwen2.py:398)"""
 
     @staticmethod
+    def grad_keys(arena, wkey, eps):
+        return [wkey]
+
+    @staticmethod
     def forward(ctx, x, anchor, arena, wkey, eps):
         y, rstd = ops.rmsnorm_fwd(x, arena[wkey].data, eps)
         ctx.save_for_backward(x, rstd)
@@ -518,6 +557,10 @@ class RMSNormFn:
 # ---------------------------------------------------------------------------------------------- lm_head (+ fused loss) (a17, a18)
 class LMHeadFn:
     """logits = hidden @ lm_head.weight^T   (materialised; used for generate() and parity checks)"""
+
+    @staticmethod
+    def grad_keys(arena, wkey):
+        return [wkey]
 
     @staticmethod
     def forward(ctx, x, anchor, arena, wkey):
@@ -544,10 +587,17 @@ class LMHeadLossFn:
     CHUNK = 4096  # 16x14 = 224 tiles of 256x256 for the dgrad GEMM: enough to fill the chip with the fast kernel
 
     @staticmethod
+    def grad_keys(arena, wkey):
+        return [wkey]
+
+    @staticmethod
     def key_state(arena, wkey):
-        """part of the stage key (stage_ops.py): whether the unscaled dW is parked in the gradient arena itself (fresh block) or in a private buffer
-        decides what forward keeps for backward"""
-        return f"fresh{int(arena[wkey].fresh)}"
+        """part of the stage key (stage_ops.py): whether the unscaled dW is parked in the gradient arena itself or in a private buffer decides what
+        forward keeps for backward.  In the arena only when nothing else can touch that slice before this stage's backward rescales it: the block is
+        fresh, no announced write to it is outstanding (another labelled forward, lm_head of out.logits) and no other dW is parked there.  A write
+        announced AFTER the parking moves the parked dW to a private copy first (Arena.expect_writes)"""
+        b = arena[wkey]
+        return f"park{int(b.fresh and b.pending == 0 and wkey not in arena.parked)}"
 
     @staticmethod
     def forward(ctx, x, anchor, arena, wkey, shift_labels, denom, rows=None):
@@ -580,8 +630,11 @@ class LMHeadLossFn:
             blk.shadow_lazy = True
         wt = arena.shadow(wkey) if need_grad and not direct and not nn_dgrad else None
         if need_grad:
-            # unscaled lm_head gradient goes to a private buffer when it must be accumulated into existing grads
-            gw_tmp = blk.grad if blk.fresh else torch.empty_like(blk.grad)
+            # unscaled lm_head gradient goes to a private buffer unless the arena slice is this stage's alone until its backward (key_state)
+            park = (ctx.key_state or LMHeadLossFn.key_state(arena, wkey)) == "park1"
+            gw_tmp = blk.grad if park else torch.empty_like(blk.grad)
+            if park:
+                arena.parked[wkey] = None
         first = True
         for s in range(0, M, chunk):
             e = min(M, s + chunk)
@@ -616,14 +669,20 @@ class LMHeadLossFn:
         arena, wkey, M_all = ctx.meta
         inplace = gw_tmp is None
         blk = arena[wkey]
+        if inplace:
+            moved = arena.parked.pop(wkey, None)
+            if moved is not None:   # another write to the block was announced after this forward: the parked dW was moved out (Arena.expect_writes)
+                gw_tmp, inplace = moved, False
         g32 = g.reshape(1).float()
         ops.scale_add_(dx, dx, g32, accumulate=False)
         if rows is not None:
             dx = ops.scatter_rows(dx, rows, M_all)
+        if not blk.fresh:
+            arena.join_streams()   # another head's weight gradient (LMHeadFn: linear_bwd on the wgrad stream) may still be landing in the slice
         if inplace:
             ops.scale_add_(blk.grad, blk.grad, g32, accumulate=False)
         else:
-            ops.scale_add_(gw_tmp, blk.grad, g32, accumulate=True)
+            ops.scale_add_(gw_tmp, blk.grad, g32, accumulate=not blk.fresh)
         arena.grad_written(blk)
         return dx, None, None, None, None, None, None
 

@@ -87,6 +87,7 @@ class _Ctx:
     saved_tensors = ()
     meta = None
     needs_input_grad = ()
+    key_state = None   # the stage's key_state() as it was when the key was made (read by the forward body)
 
     def save_for_backward(self, *tensors):
         self.saved_tensors = tensors
@@ -176,6 +177,23 @@ class _Stage:
         ctx = _Ctx()
         full = self._full_args(tens, arena, static)
         ctx.needs_input_grad = (key.endswith("|g1"),) * len(full)
+        ks = getattr(self.fn, "key_state", None)
+        ctx.key_state = ks(arena, *static) if ks is not None else None   # before the announcement below changes the state it reads
+        from . import functional as F
+
+        gk = None
+        if not F.RECOMPUTING:
+            # a new forward: no column-sum hand-over of an earlier backward may survive into this one (functional.EncoderLayerFn)
+            if getattr(arena, "presums", None) is not None:
+                arena.presums.clear()
+            if ctx.needs_input_grad[0] and hasattr(self.fn, "grad_keys"):
+                # the writes this stage's backward will make to the gradient arena: a bucket is complete when all announced writes have landed (a
+                # checkpointed layer's re-run inside backward announces nothing - its forward did)
+                c0 = _CACHE.get(key)
+                gk = c0.get("grad_keys") if c0 is not None else None
+                if gk is None:
+                    gk = tuple(self.fn.grad_keys(arena, *static))
+                arena.expect_writes([arena[k] for k in gk])
         out = self.fn.forward(ctx, *full)
         g_store, p_store = grads.untyped_storage().data_ptr(), params.untyped_storage().data_ptr()
         outs, src = [out], []
@@ -193,6 +211,8 @@ class _Stage:
                 outs.append(t)
         c = _CACHE.setdefault(key, {})
         _touch(_CACHE, key)
+        if gk is not None:
+            c["grad_keys"] = gk
         meta = ctx.meta
         fwd_meta = tuple(_ARENA if m is arena else m for m in meta) if isinstance(meta, tuple) else meta
         if "src" in c and (c["src"] != src or not _same_meta(c["fwd_meta"], fwd_meta)):

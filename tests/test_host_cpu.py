@@ -148,6 +148,95 @@ def test_bucket_ready_callbacks_fire_in_backward_order():
     assert all(b.fresh for b in a.order)
 
 
+def _announce_forward(a, times=1):
+    """what the stages' forwards announce for one labelled step of the tiny model (stage_ops: every block of every stage, once), `times` forwards"""
+    for _ in range(times):
+        a.expect_writes(list(a.order))
+
+
+def test_bucket_with_two_writes_to_a_block_fires_after_the_last_announced_one():
+    """forward(labels, return_logits=True): lm_head.weight is written by lm_head + loss AND by the lm_head of out.logits.  The head bucket
+    (final norm + lm_head) has two blocks: it must not fire after two writes to lm_head while the final norm is still unwritten"""
+    from audio_flamingo_amd.modeling import AudioFlamingo3ForConditionalGeneration as Mine
+
+    m = Mine(_cfg(), device="cpu")
+    a = m.arena
+    fired = []
+    a.on_bucket_ready = fired.append
+    a.zero_grad()
+    head = a.bucket_names.index("head")
+    lm, norm = a["lm_head.weight"], a["model.language_model.norm.weight"]
+    a.expect_writes([norm])
+    a.expect_writes([lm])        # lm_head + loss
+    a.expect_writes([lm])        # lm_head (out.logits)
+    a.grad_written(lm)
+    a.grad_written(lm)
+    assert fired == [], "head bucket handed over before the final norm's gradient was written"
+    a.grad_written(norm)
+    assert fired == [head]
+    assert lm.pending == 0 and norm.pending == 0
+
+
+def test_bucket_with_an_unwritten_block_never_fires_early_and_nothing_fires_twice():
+    """two forwards of the whole model, then one backward that writes every block twice in reverse layout order: every bucket fires exactly
+    once, after its LAST write, in backward order; a bucket missing one write does not fire at all (finish() handles it)"""
+    from audio_flamingo_amd.modeling import AudioFlamingo3ForConditionalGeneration as Mine
+
+    m = Mine(_cfg(), device="cpu")
+    a = m.arena
+    fired = []
+    a.on_bucket_ready = lambda i: fired.append((i, sum(1 for b in a.bucket_blocks(i) for _ in range(2 - b.pending))))
+    a.zero_grad()
+    _announce_forward(a, times=2)
+    order = list(reversed(a.order))
+    for blk in order:
+        a.grad_written(blk)
+    assert fired == [], fired            # every bucket still expects its second set of writes
+    skip = a["model.audio_tower.layers.0.fc2.bias"]
+    for blk in order:
+        if blk is not skip:
+            a.grad_written(blk)
+    enc0 = a.bucket_names.index("enc0")
+    want = [i for i in reversed(range(len(a.bucket_names))) if i != enc0]
+    assert [i for i, _ in fired] == want, fired
+    assert all(n == 2 * len(a.bucket_blocks(i)) for i, n in fired), fired    # fired after ALL writes of the bucket
+    a.grad_written(skip)
+    assert [i for i, _ in fired] == want + [enc0]
+    assert len({i for i, _ in fired}) == len(fired), "a bucket fired twice"
+    # begin_backward() between the forwards and the backward keeps what the forwards announced
+    fired.clear()
+    a.zero_grad()
+    _announce_forward(a, times=2)
+    a.begin_backward()
+    for blk in order + order:
+        a.grad_written(blk)
+    assert [i for i, _ in fired] == list(reversed(range(len(a.bucket_names))))
+
+
+def test_hand_over_and_parking_slots_are_cleared_by_zero_grad():
+    """the column-sum hand-over slot and the parked lm_head gradient belong to one backward: zero_grad() drops both; a write announced while
+    lm_head's dW is parked in the arena moves it to a private copy first"""
+    from audio_flamingo_amd.modeling import AudioFlamingo3ForConditionalGeneration as Mine
+    from audio_flamingo_amd import functional as F
+
+    m = Mine(_cfg(), device="cpu")
+    a = m.arena
+    a.zero_grad()
+    lm = a["lm_head.weight"]
+    assert F.LMHeadLossFn.key_state(a, "lm_head.weight") == "park1"
+    a.expect_writes([lm])                              # lm_head + loss announces its write, then its forward parks dW in the arena
+    lm.grad.fill_(3.0)
+    a.parked["lm_head.weight"] = None
+    assert F.LMHeadLossFn.key_state(a, "lm_head.weight") == "park0"   # a second labelled forward keeps its dW private
+    a.expect_writes([lm])                              # another writer (a second forward, out.logits)
+    moved = a.parked["lm_head.weight"]
+    assert moved is not None and moved.data_ptr() != lm.grad.data_ptr() and bool((moved == 3.0).all())
+    a.presums.update({"for": "x", "dx": torch.zeros(2), "version": 0, "row": torch.zeros(2)})
+    a.zero_grad()
+    assert not a.presums and not a.parked and lm.pending == 0
+    assert F.LMHeadLossFn.key_state(a, "lm_head.weight") == "park1"
+
+
 WORKER = r'''
 import os, sys, torch, torch.distributed as dist
 sys.path.insert(0, sys.argv[1])
