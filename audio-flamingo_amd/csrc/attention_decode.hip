@@ -643,6 +643,10 @@ static int attn_decode_impl(bool fused, const void* Q, int64_t q_bs, int64_t q_h
     AFK_REQUIRE(Q && Kc && Vt && O && krange && workspace, "afk_attn_decode: null pointer");
     AFK_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && (D == 64 || D == 128) && nsplit >= 1 && nsplit <= 64, "afk_attn_decode: bad shape");
     AFK_REQUIRE(!fused || nsplit * (D + 2) <= MAXCHUNK, "afk_attn_decode_fused: nsplit * (D + 2) <= %d (the merge stages the partials in the score buffer)", MAXCHUNK);
+    // a chunk holds at most MAXCHUNK keys (GCHUNK in the group forms, which check their own bound below): nsplit chunks must cover the whole cache row, or the
+    // keys behind nsplit * MAXCHUNK are silently not read.  The visible range lies in [0, spad), so covering spad covers every [lo & ~7, hi).
+    AFK_REQUIRE((int64_t)spad <= (int64_t)nsplit * MAXCHUNK, "afk_attn_decode: spad %d > nsplit %d * %d keys per chunk (use nsplit >= ceil(spad / %d))", spad, nsplit,
+                MAXCHUNK, MAXCHUNK);
     AFK_REQUIRE(q_bs % 8 == 0 && q_hs % 8 == 0 && k_bs % 8 == 0 && k_rs % 8 == 0 && k_hs % 8 == 0 && vt_bs % 8 == 0 && spad % 8 == 0,
                 "afk_attn_decode: strides must keep 16-byte alignment");
     hipStream_t st = (hipStream_t)stream;

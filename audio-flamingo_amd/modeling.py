@@ -909,7 +909,7 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             elif n == 1 and D in (64, 128) and self.decode_splits > 0:
                 # one query row per sample: split-KV kernel (the cache is read once, nsplit blocks per head)
                 o = torch.empty((B, nq), device=x.device, dtype=torch.bfloat16)
-                ns = self.decode_splits
+                ns = self._decode_nsplit(Spad)
                 ws = torch.empty(_lib.load().afk_attn_decode_workspace_floats(B, Hq, D, ns), device=x.device, dtype=torch.float32)
                 _lib.call("afk_attn_decode", qkv.data_ptr(), qkv.stride(0), D, Kc[i].data_ptr(), Smax * nk, nk, D, Vt[i].data_ptr(),
                           Hkv * D * Spad, Spad, o.data_ptr(), nq, D, krange.data_ptr(), B, Hq, Hkv, D, float(D ** -0.5), ns,
@@ -942,7 +942,7 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         dev = x.device
         cos, sin = self._rope_tables(int(self.config.text_config.max_position_embeddings))
         st = ops._stream()
-        ns = self.decode_splits
+        ns = self._decode_nsplit(Spad)
         aws = torch.empty(_lib.load().afk_attn_decode_workspace_floats(B, Hq, D, ns), device=dev, dtype=torch.float32)
 
         def gemv(inp, w):
@@ -995,9 +995,9 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         dev = x.device
         cos, sin = self._rope_tables(int(self.config.text_config.max_position_embeddings))
         st = ops._stream()
-        ns = self.decode_splits
         if aws is None:
-            aws = self._decode_attn_workspace(dev)
+            aws = self._decode_attn_workspace(dev, Spad)
+        ns = self._decode_attn_ws_check(aws, 1, Spad)
         q = torch.empty((1, nq), device=dev, dtype=torch.bfloat16)
         o = torch.empty((1, nq), device=dev, dtype=torch.bfloat16)
         eps = float(self.rms_eps)
@@ -1055,7 +1055,7 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         dev = x.device
         cos, sin = self._rope_tables(int(self.config.text_config.max_position_embeddings))
         st = ops._stream()
-        ns = self.decode_splits
+        ns = self._decode_attn_ws_check(aws, B, Spad)
         eps = float(self.rms_eps)
         q = torch.empty((B, nq), device=dev, dtype=torch.bfloat16)
         o = torch.empty((B, nq), device=dev, dtype=torch.bfloat16)
@@ -1151,9 +1151,30 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         return (self.decode_chain and B == 1 and self.D in (64, 128) and self.decode_splits > 0 and self.H % 8 == 0
                 and self.decode_splits * (self.D + 2) <= 4096)
 
-    def _decode_attn_workspace(self, dev):
-        """partials + arrival counters of afk_attn_decode_fused for one sequence; the counters start at zero and every launch leaves them at zero"""
-        return torch.zeros(_lib.load().afk_attn_decode_workspace_floats(1, self.Hq, self.D, self.decode_splits), device=dev, dtype=torch.float32)
+    DECODE_CHUNK_KEYS = 4096   # keys one split of the Q = 1 attention holds (csrc/attention_decode.hip MAXCHUNK): it refuses spad > nsplit * 4096
+
+    def _decode_nsplit(self, spad):
+        """key splits of the Q = 1 attention over a cache of pitch spad: decode_splits, or more when decode_splits chunks of 4 096 keys do not cover the
+        cache (the kernel refuses that - it used to drop the keys behind them).  The one-launch form merges the splits' partials in LDS: nsplit * (D + 2)
+        <= 4096; a longer cache is refused here rather than read in part."""
+        ns = max(self.decode_splits, -(-int(spad) // self.DECODE_CHUNK_KEYS))
+        if ns * (self.D + 2) > 4096:
+            raise AfkError(f"decode attention: a KV cache of {spad} positions needs {ns} key splits of at most {self.DECODE_CHUNK_KEYS}; the split merge holds "
+                           f"at most {4096 // (self.D + 2)} at head_dim {self.D} (cache limit {4096 // (self.D + 2) * self.DECODE_CHUNK_KEYS} positions)")
+        return ns
+
+    def _decode_attn_workspace(self, dev, spad, B=1):
+        """partials + arrival counters of afk_attn_decode_fused for B sequences over a cache of pitch spad (as many splits as _decode_nsplit(spad)); the
+        counters start at zero and every launch leaves them at zero"""
+        return torch.zeros(_lib.load().afk_attn_decode_workspace_floats(B, self.Hq, self.D, self._decode_nsplit(spad)), device=dev, dtype=torch.float32)
+
+    def _decode_attn_ws_check(self, aws, B, spad):
+        """-> the split count of a decode step whose workspace was allocated earlier (a captured graph replays it): the workspace must hold that many"""
+        ns = self._decode_nsplit(spad)
+        need = _lib.load().afk_attn_decode_workspace_floats(B, self.Hq, self.D, ns)
+        if aws.numel() < need:
+            raise AfkError(f"decode attention: workspace of {aws.numel()} floats for {ns} splits over spad {spad} (needs {need}): allocate it for this cache")
+        return ns
 
     def _decode_step(self, st):
         """one greedy decode step on static buffers (everything position-dependent lives on the device): HIP-graph capturable"""
@@ -1249,11 +1270,11 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             kr1 = torch.stack([st["lo"], (st["cur"] + 1).expand(B)], -1).reshape(B, 1, 2).contiguous()
         if (self._chain_ok(1) and 2 <= B <= self._chain_batch_cap(st["head"]) and st["head"].shape[0] % 8 == 0 and self.I % 4 == 0):
             if "aws" not in st:
-                st["aws"] = torch.zeros(_lib.load().afk_attn_decode_workspace_floats(B, self.Hq, self.D, self.decode_splits), device=x.device, dtype=torch.float32)
+                st["aws"] = self._decode_attn_workspace(x.device, st["cache"][1].shape[4], B)
             return self._decode_layers_chain_batched(x.contiguous(), B, st["cache"], pos1, kr1, st["cur"], st["aws"], st["head"])
         if self._chain_ok(B):
             if "aws" not in st:
-                st["aws"] = self._decode_attn_workspace(x.device)
+                st["aws"] = self._decode_attn_workspace(x.device, st["cache"][1].shape[4])
             head = st["head"] if st["head"].shape[0] % 8 == 0 else None
             y = self._decode_layers_chain(x.contiguous(), st["cache"], pos1, kr1, st["cur"], aws=st["aws"], head=head)
             if head is not None:
@@ -1372,7 +1393,7 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             if sampling is None and not hooks and self._chain_ok(1) and st["head"].shape[0] % 8 == 0:   # greedy: token selection and step bookkeeping stay on the device
                 tok_buf = torch.zeros(max_new_tokens, device=dev, dtype=torch.int64)
                 tok_buf[0] = st["nxt"][0]
-                st.update(x0=st["emb"].index_select(0, st["nxt"]).contiguous(), aws=self._decode_attn_workspace(dev), tok_buf=tok_buf, tok_off=1 - S0,
+                st.update(x0=st["emb"].index_select(0, st["nxt"]).contiguous(), aws=self._decode_attn_workspace(dev, Vt.shape[4]), tok_buf=tok_buf, tok_off=1 - S0,
                           part_val=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.float32),
                           part_idx=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.int32))
         if hooks:

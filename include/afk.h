@@ -314,7 +314,8 @@ int afk_kv_cache_append(const void* qkv, int64_t ld, int k_col0, void* kcache, i
 /* Decode-time attention over the KV cache, one query row per sample (Qwen2Attention.forward with past_key_values, modeling_qwen2.py:
  * 195-234): split-KV.  Q [B][Hq][D] (strides q_bs, q_hs), K cache [B][pos][Hkv][D] (k_bs, k_rs, k_hs), V^T cache [B][Hkv][D][spad]
  * (vt_bs) as written by afk_kv_cache_append, O like Q.  krange[B][2] = visible key interval [lo, hi) per sample, read on the device.
- * workspace: afk_attn_decode_workspace_floats(B, Hq, D, nsplit) floats.  head_dim 64 / 128. */
+ * workspace: afk_attn_decode_workspace_floats(B, Hq, D, nsplit) floats.  head_dim 64 / 128.  A chunk holds at most 4 096 keys: spad <= nsplit * 4096
+ * is required (refused otherwise), i.e. nsplit >= ceil(spad / 4096). */
 int afk_attn_decode_workspace_floats(int B, int Hq, int D, int nsplit);
 int afk_attn_decode(const void* Q, int64_t q_bs, int64_t q_hs, const void* Kc, int64_t k_bs, int64_t k_rs, int64_t k_hs,
                     const void* Vt, int64_t vt_bs, int spad, void* O, int64_t o_bs, int64_t o_hs, const int* krange, int B,
