@@ -277,15 +277,54 @@ class Arena:
             self.params[s:e] = (torch.randn(e - s, device=self.device, dtype=torch.float32, generator=g) * std).to(torch.bfloat16)
 
 
-class FusedAdamW:
-    """AdamW over the arena: bf16 params + fp32 master/m/v.  One launch per decay class."""
+def resolve_state_dtype(state_dtype=None) -> str:
+    """"fp32" or "bf16"; None reads AFK_ADAMW_STATE (fp32 when unset).  Anything else is an error, never a silent default."""
+    name = os.environ.get("AFK_ADAMW_STATE", "fp32") if state_dtype is None else state_dtype
+    name = {torch.float32: "fp32", torch.bfloat16: "bf16"}.get(name, name)
+    name = {"float32": "fp32", "bfloat16": "bf16"}.get(name, name)
+    if name not in ("fp32", "bf16"):
+        src = "AFK_ADAMW_STATE" if state_dtype is None else "state_dtype"
+        raise AfkError(f"{src}={name!r}: the AdamW state is 'fp32' (fp32 master / m / v, the default) or 'bf16' (bf16 m / v, no master)")
+    return name
 
-    def __init__(self, arena: Arena, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+
+def check_state_dtype(sd, want: str, who: str):
+    """a checkpoint written in the other state mode is refused: a silent cast would change the optimizer's numerics (bf16 -> fp32 has no master to
+    restore, fp32 -> bf16 throws the master away).  Checkpoints from before the switch carry no "state_dtype": they are fp32."""
+    got = sd.get("state_dtype") or ("fp32" if "master" in sd.get("state", {}) else "bf16")
+    for t in (sd.get("state", {}).get("m"), sd.get("state", {}).get("v")):
+        if torch.is_tensor(t) and t.dtype != (torch.bfloat16 if got == "bf16" else torch.float32):
+            raise AfkError(f"{who}: the checkpoint says state_dtype={got} but holds {t.dtype} moments")
+    if got != want:
+        raise AfkError(f"{who}: the checkpoint holds {got} optimizer state, this optimizer keeps {want} state (state_dtype / AFK_ADAMW_STATE); "
+                       f"load it into an optimizer built with state_dtype={got!r}")
+
+
+class FusedAdamW:
+    """AdamW over the arena.  One launch per decay class.
+
+    state_dtype="fp32" (the default): bf16 params + fp32 master / m / v, 28 B/param of traffic per step, 12 B/param of state.
+
+    state_dtype="bf16": what torch.optim.AdamW(fused=True) does on a bf16 model - the arena's bf16 parameters are the only copy of the weights
+    (`master` is None), m / v are bf16; every element is widened to fp32, updated in fp32 and rounded to bf16 once on the store
+    (afk_adamw16_step): 14 B/param of traffic, 4 B/param of state.  None reads AFK_ADAMW_STATE.
+    NUMERICAL CAVEAT of the bf16 mode: with beta2 = 0.999 a bf16 `v` cannot take in an increment smaller than half its ulp, i.e. 2^-8 of its
+    value - (1 - beta2) * g^2 is lost whenever it is that small beside v, so v tracks slowly changing gradient scales worse than fp32 state
+    does, and parameter updates below half a bf16 ulp of the weight are dropped for want of a master.  That is the reference optimizer's own
+    behaviour on a bf16 model, and it is the reason fp32-master stays the default."""
+
+    def __init__(self, arena: Arena, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, state_dtype=None):
         self.arena = arena
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
-        self.master = arena.params.float()
-        self.m = torch.zeros_like(self.master)
-        self.v = torch.zeros_like(self.master)
+        self.state_dtype = resolve_state_dtype(state_dtype)
+        if self.state_dtype == "bf16":
+            self.master = None  # the bf16 parameters are the weights
+            self.m = torch.zeros_like(arena.params)
+            self.v = torch.zeros_like(arena.params)
+        else:
+            self.master = arena.params.float()
+            self.m = torch.zeros_like(self.master)
+            self.v = torch.zeros_like(self.master)
         self.t = 0
         self._synced = (arena.params._version, arena.step_counter)
         # step-dependent scalars (lr, bias corrections) live on the device: every AdamW launch reads them there, so a captured HIP graph
@@ -359,12 +398,22 @@ class FusedAdamW:
             else:
                 b, wd = op[1], op[2]
                 s, e = b.offset, b.offset + b.numel
+                if self.master is None:
+                    ops.adamw16_step_t(self.m[s:e], self.v[s:e], a.grads[s:e], a.params[s:e], a.ensure_T_shadow(b), b.shape[0], b.shape[1],
+                                       lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=wd, step=self.t,
+                                       grad_scale=grad_scale, max_blocks=max_blocks, gate=gate, hyper=self.hyper)
+                    continue
                 ops.adamw_step_t(self.master[s:e], self.m[s:e], self.v[s:e], a.grads[s:e], a.params[s:e], a.ensure_T_shadow(b), b.shape[0], b.shape[1],
                                  lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=wd, step=self.t, grad_scale=grad_scale,
                                  max_blocks=max_blocks, gate=gate, hyper=self.hyper)
 
     def _launch(self, s, e, wd, grad_scale, max_blocks=0, gate=None):
         a = self.arena
+        if self.master is None:
+            ops.adamw16_step(self.m[s:e], self.v[s:e], a.grads[s:e], a.params[s:e], lr=self.lr,
+                             beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=wd, step=self.t,
+                             grad_scale=grad_scale, max_blocks=max_blocks, gate=gate, hyper=self.hyper)
+            return
         ops.adamw_step(self.master[s:e], self.m[s:e], self.v[s:e], a.grads[s:e], a.params[s:e], lr=self.lr,
                        beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=wd, step=self.t,
                        grad_scale=grad_scale, max_blocks=max_blocks, gate=gate, hyper=self.hyper)
@@ -395,8 +444,15 @@ class FusedAdamW:
         ops.clip_coef_(self._sumsq, self.hyper[3:4], max_norm=self.clip_norm, scale=grad_scale, norm_out=self.grad_norm)
 
     # ------------------------------------------------------------------ master <-> working copy
+    def state_bytes(self) -> int:
+        """bytes of optimizer state this object holds: fp32 master + m + v, or bf16 m + v"""
+        return (4 if self.master is None else 12) * self.arena.total
+
     def sync_master(self):
-        """re-read the fp32 master from the bf16 parameters (call after anything that rewrote them: load_state_dict, broadcast)"""
+        """re-read the fp32 master from the bf16 parameters (call after anything that rewrote them: load_state_dict, broadcast).
+        bf16 state: nothing to re-derive, the parameters are the weights."""
+        if self.master is None:
+            return
         self.master.copy_(self.arena.params)
         self._mark_synced()
 
@@ -406,7 +462,7 @@ class FusedAdamW:
     def _check_master(self):
         """parameters rewritten behind the optimizer's back (model.load_state_dict, a broadcast, an in-place init) would be overwritten
         by `old master + update` on the next step: detect it (tensor version / arena step counter) and re-read the master first."""
-        if self._synced != (self.arena.params._version, self.arena.step_counter):
+        if self.master is not None and self._synced != (self.arena.params._version, self.arena.step_counter):
             self.sync_master()
 
     def _runs(self, blocks):
@@ -503,9 +559,10 @@ class ShardedAdamW(FusedAdamW):
     Global-norm clipping: every rank sums the squares of its own shares (the tail on rank 0 only), one extra SUM all-reduce of the per-bucket partial
     sums closes the norm - identical on every rank, NOT bit-identical to the replicated path's norm (other summation order)."""
 
-    def __init__(self, arena: Arena, engine, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, arena: Arena, engine, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, state_dtype=None):
         self.arena = arena
         self.engine = engine
+        self.state_dtype = resolve_state_dtype(state_dtype)
         self.rank, self.world = int(engine.rank), int(engine.world)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         # owned intervals of the arena, ascending: (arena start, arena end, state offset)
@@ -519,10 +576,12 @@ class ShardedAdamW(FusedAdamW):
                     self.owned.append((a0, a1, off))
                     off += a1 - a0
         self.state_numel = off
-        self.master = torch.empty(off, device=arena.device, dtype=torch.float32)
-        self.m = torch.zeros(off, device=arena.device, dtype=torch.float32)
-        self.v = torch.zeros(off, device=arena.device, dtype=torch.float32)
+        sdt = torch.bfloat16 if self.state_dtype == "bf16" else torch.float32
+        self.master = torch.empty(off, device=arena.device, dtype=torch.float32) if self.state_dtype == "fp32" else None   # bf16 state: no compact master
+        self.m = torch.zeros(off, device=arena.device, dtype=sdt)
+        self.v = torch.zeros(off, device=arena.device, dtype=sdt)
         self.t = 0
+        self._synced = (arena.params._version, arena.step_counter)
         self.hyper = torch.zeros(4, device=arena.device, dtype=torch.float32) if arena.device.type == "cuda" else None
         self._in_capture = False
         self.clip_norm: Optional[float] = None
@@ -548,9 +607,11 @@ class ShardedAdamW(FusedAdamW):
         return out
 
     def state_bytes(self) -> int:
-        return 12 * self.state_numel
+        return (4 if self.master is None else 12) * self.state_numel
 
     def sync_master(self):
+        if self.master is None:
+            return
         for a0, a1, off in self.owned:
             self.master[off: off + a1 - a0].copy_(self.arena.params[a0:a1])
         self._mark_synced()
@@ -560,6 +621,11 @@ class ShardedAdamW(FusedAdamW):
         a = self.arena
         for lo, hi, off in self._pieces(s, e):
             n = hi - lo
+            if self.master is None:   # shares are multiples of 128 bytes: every piece keeps the 16-byte alignment the bf16 launch needs
+                ops.adamw16_step(self.m[off: off + n], self.v[off: off + n], a.grads[lo:hi], a.params[lo:hi], lr=self.lr,
+                                 beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=wd, step=self.t,
+                                 grad_scale=grad_scale, max_blocks=max_blocks, gate=gate, hyper=self.hyper)
+                continue
             ops.adamw_step(self.master[off: off + n], self.m[off: off + n], self.v[off: off + n], a.grads[lo:hi], a.params[lo:hi], lr=self.lr,
                            beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=wd, step=self.t,
                            grad_scale=grad_scale, max_blocks=max_blocks, gate=gate, hyper=self.hyper)
@@ -615,9 +681,10 @@ class ShardedAdamW(FusedAdamW):
 
     # ------------------------------------------------------------------ checkpoint / resume (the sharded state must be saveable)
     def _consolidate(self, compact: torch.Tensor, to_cpu: bool) -> torch.Tensor:
-        """one compact per-rank state array -> the FULL flat fp32 array in the arena's layout (what FusedAdamW holds and trainer.AfkAdamW saves), on every
+        """one compact per-rank state array -> the FULL flat array in the arena's layout (what FusedAdamW holds and trainer.AfkAdamW saves), on every
         rank: each rank writes the pieces it owns into zeros (a bucket's replicated tail from rank 0 only) and a SUM over the ranks assembles them -
-        x + 0 + ... + 0 is exact, so the result is bit-identical to the owners' values.  Chunked (256 Mi elements) so that a host-staged backend works."""
+        x + 0 + ... + 0 is exact, so the result is bit-identical to the owners' values.  Chunked (256 Mi elements) so that a host-staged backend works.
+        The sum runs in fp32 for either state dtype (bf16 -> fp32 -> bf16 is exact); the result has the dtype of `compact`."""
         a = self.arena
         full = torch.zeros(a.total, device=a.device, dtype=torch.float32)
         for i in range(len(a.bucket_names)):
@@ -641,34 +708,40 @@ class ShardedAdamW(FusedAdamW):
                     piece.copy_(h.to(piece.device))
                 else:
                     dist.all_reduce(piece, op=dist.ReduceOp.SUM, group=eng.pg)
+        full = full.to(compact.dtype)
         return full.cpu() if to_cpu else full
 
     def state_dict(self, to_cpu: bool = True):
         """COLLECTIVE (every rank calls it): the consolidated optimizer state in the replicated layout - {"state": {"master", "m", "v": fp32 [arena.total],
         "t"}, "hyper": {...}} - the same "state" trainer.AfkAdamW.state_dict() saves, so a run may be checkpointed sharded and resumed replicated (or at another
-        world size) and vice versa.  One moment at a time (33 GB fp32 for AF3-7B), moved to the host before the next when to_cpu (the default)."""
+        world size) and vice versa.  One moment at a time (33 GB fp32 for AF3-7B), moved to the host before the next when to_cpu (the default).
+        bf16 state: {"m", "v": bf16 [arena.total], "t"} and "state_dtype": "bf16" - no master, the parameters live in the model checkpoint."""
         self.arena.join_streams()
-        return {"state": {"master": self._consolidate(self.master, to_cpu), "m": self._consolidate(self.m, to_cpu), "v": self._consolidate(self.v, to_cpu),
-                          "t": self.t},
+        state = {} if self.master is None else {"master": self._consolidate(self.master, to_cpu)}
+        state.update(m=self._consolidate(self.m, to_cpu), v=self._consolidate(self.v, to_cpu), t=self.t)
+        return {"state": state, "state_dtype": self.state_dtype,
                 "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay},
-                "layout": {"format": "flat-arena-fp32", "numel": self.arena.total, "saved_from_world": self.world}}
+                "layout": {"format": f"flat-arena-{self.state_dtype}", "numel": self.arena.total, "saved_from_world": self.world}}
 
     def load_state_dict(self, sd):
         """restore from the consolidated layout (state_dict() above or trainer.AfkAdamW.state_dict()): every rank slices out the pieces it owns; the bf16
         working copy of EVERY parameter follows the restored fp32 master, as AfkAdamW.load_state_dict does."""
         st = sd["state"]
         a = self.arena
-        for name in ("master", "m", "v"):
+        check_state_dtype(sd, self.state_dtype, "ShardedAdamW.load_state_dict")
+        names = ("m", "v") if self.master is None else ("master", "m", "v")
+        for name in names:
             if st[name].numel() != a.total:
                 raise AfkError(f"ShardedAdamW.load_state_dict: {name} has {st[name].numel()} elements, the arena {a.total}")
         for a0, a1, off in self.owned:
             n = a1 - a0
-            self.master[off: off + n].copy_(st["master"][a0:a1])
-            self.m[off: off + n].copy_(st["m"][a0:a1])
-            self.v[off: off + n].copy_(st["v"][a0:a1])
+            for name in names:
+                getattr(self, name)[off: off + n].copy_(st[name][a0:a1])
         self.t = int(st["t"])
         for k, v in (sd.get("hyper") or {}).items():
             setattr(self, k, tuple(v) if k == "betas" else v)
+        if self.master is None:   # bf16 state: the parameters are not optimizer state, they come from the model checkpoint
+            return
         for c0 in range(0, a.total, 1 << 28):
             a.params.data[c0: c0 + (1 << 28)].copy_(st["master"][c0: c0 + (1 << 28)])
         a.step_counter += 1

@@ -637,6 +637,113 @@ __global__ __launch_bounds__(256) void adamw_t_kernel(float* __restrict__ master
     }
 }
 
+// ------------------------------------------------------------------ AdamW with bf16 state (14 B/param): what torch.optim.AdamW(fused=True) does on a bf16 model
+// (TORCH/optim/adamw.py fused path -> _fused_adamw_; the element math of ATen's fused_adam_utils adam_math).  The bf16 parameters are the only copy of
+// the weights, m / v are bf16: each is widened to fp32, the whole update runs in fp32 and every result is rounded to bf16 ONCE, on its store.
+// The forms are torch's, not adamw_elem's - p -= (lr*wd)*p, m = lerp(m, g, 1-b1) = m + (1-b1)*(g-m), p -= (lr/bc1 * m) / denom: with bf16 inputs the fp32
+// results sit on bf16 rounding ties often, and which way a tie falls depends on the form.  Contraction OFF for the reason given above adamw_elem.
+// omb1 = 1 - beta1 and omb2 = 1 - beta2 come from the host, taken in double as torch takes them: 1.f - 0.999f is 1.3e-5 away from 0.001, which
+// moves the update by 6e-6 of itself - more than the whole fp32 error budget wherever p and the update nearly cancel.
+__device__ __forceinline__ void adamw16_elem(float& w, float& mm, float& vv, float gr, float lr, float omb1, float b2, float omb2, float eps, float wd,
+                                             float bc1, float bc2_sqrt) {
+#pragma clang fp contract(off)
+    w = w - (lr * wd) * w;
+    mm = mm + omb1 * (gr - mm);
+    vv = b2 * vv + (omb2 * gr) * gr;
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    w = w - ((lr / bc1) * mm) / denom;
+}
+
+// eight elements of the four bf16 streams: the update of one 16-byte vector per stream, shared by the flat and the tiled launch
+__device__ __forceinline__ void adamw16_vec(bf16x8& pp, bf16x8& mm, bf16x8& vv, const bf16x8 gg, float lr, float omb1, float b2, float omb2, float eps,
+                                            float wd, float bc1, float bc2_sqrt, float grad_scale) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        float we = (float)pp[e], me = (float)mm[e], ve = (float)vv[e];
+        adamw16_elem(we, me, ve, (float)gg[e] * grad_scale, lr, omb1, b2, omb2, eps, wd, bc1, bc2_sqrt);
+        pp[e] = (bf16)we, mm[e] = (bf16)me, vv[e] = (bf16)ve;
+    }
+}
+
+// Flat launch: 8 elements per lane, so each of the four loads and three stores is one 16-byte access (2 + 2 + 2 + 2 B read, 2 + 2 + 2 B written per parameter).
+// gate / hyper / max_blocks exactly as adamw_kernel.  <= 64 VGPRs for the same reason as adamw_t_kernel (thin launches beside GEMM workgroups).
+__global__ __launch_bounds__(256) void adamw16_kernel(bf16* __restrict__ p, bf16* __restrict__ m, bf16* __restrict__ v, const bf16* __restrict__ g,
+                                                      int64_t n, float lr, float omb1, float b2, float omb2, float eps, float wd, float bc1,
+                                                      float bc2_sqrt, float grad_scale, const int* __restrict__ gate, const float* __restrict__ hyper) {
+    if (gate != nullptr && *gate == 0) return;
+    if (hyper != nullptr) {
+        lr = hyper[0];
+        bc1 = hyper[1];
+        bc2_sqrt = hyper[2];
+        grad_scale *= hyper[3];
+    }
+    const int64_t nv = n >> 3;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (int64_t)gridDim.x * 256) {
+        bf16x8 pp = *(const bf16x8*)(p + 8 * i), mm = *(const bf16x8*)(m + 8 * i), vv = *(const bf16x8*)(v + 8 * i);
+        const bf16x8 gg = *(const bf16x8*)(g + 8 * i);
+        adamw16_vec(pp, mm, vv, gg, lr, omb1, b2, omb2, eps, wd, bc1, bc2_sqrt, grad_scale);
+        *(bf16x8*)(p + 8 * i) = pp;
+        *(bf16x8*)(m + 8 * i) = mm;
+        *(bf16x8*)(v + 8 * i) = vv;
+    }
+    // tail (n % 8)
+    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
+        const int64_t i = (nv << 3) + threadIdx.x;
+        float w = (float)p[i], mm = (float)m[i], vv = (float)v[i];
+        adamw16_elem(w, mm, vv, (float)g[i] * grad_scale, lr, omb1, b2, omb2, eps, wd, bc1, bc2_sqrt);
+        p[i] = (bf16)w;
+        m[i] = (bf16)mm;
+        v[i] = (bf16)vv;
+    }
+}
+
+// The same update on ONE 2-D weight [N, K] that also writes the K-major shadow: adamw_t_kernel's 64x64 tiles and LDS transpose, with 8 lanes x 8
+// elements per row (128 contiguous bytes of every stream), 32 rows per pass, 2 passes.  Bit-identical to adamw16_kernel (adamw16_vec is shared;
+// tests/test_adamw16_gpu.py::test_adamw16_transposed_shadow).  N % 64 == 0 and K % 64 == 0.
+__global__ __launch_bounds__(256) void adamw16_t_kernel(bf16* __restrict__ p, bf16* __restrict__ m, bf16* __restrict__ v, const bf16* __restrict__ g,
+                                                        bf16* __restrict__ shadow, int N, int K, int64_t ld_shadow, float lr, float omb1, float b2,
+                                                        float omb2, float eps, float wd, float bc1, float bc2_sqrt, float grad_scale,
+                                                        const int* __restrict__ gate, const float* __restrict__ hyper) {
+    if (gate != nullptr && *gate == 0) return;
+    if (hyper != nullptr) {
+        lr = hyper[0];
+        bc1 = hyper[1];
+        bc2_sqrt = hyper[2];
+        grad_scale *= hyper[3];
+    }
+    __shared__ bf16 tile[64][66];  // tile[k][n]
+    const int t = threadIdx.x;
+    const int tiles_x = K >> 6;
+    const int64_t ntiles = (int64_t)tiles_x * (N >> 6);
+    for (int64_t tix = blockIdx.x; tix < ntiles; tix += gridDim.x) {
+        const int n0 = (int)(tix / tiles_x) * 64, k0 = (int)(tix % tiles_x) * 64;
+#pragma unroll 1
+        for (int j = 0; j < 2; ++j) {
+            const int r = (t >> 3) + 32 * j, c8 = (t & 7) * 8;
+            const int64_t off = (int64_t)(n0 + r) * K + k0 + c8;
+            bf16x8 pp = *(const bf16x8*)(p + off), mm = *(const bf16x8*)(m + off), vv = *(const bf16x8*)(v + off);
+            const bf16x8 gg = *(const bf16x8*)(g + off);
+            adamw16_vec(pp, mm, vv, gg, lr, omb1, b2, omb2, eps, wd, bc1, bc2_sqrt, grad_scale);
+            *(bf16x8*)(p + off) = pp;
+            *(bf16x8*)(m + off) = mm;
+            *(bf16x8*)(v + off) = vv;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) tile[c8 + e][r] = pp[e];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int idx = t + 256 * j;
+            const int c = idx >> 3, ch = idx & 7;
+            bf16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = tile[c][ch * 8 + e];
+            *(bf16x8*)(shadow + (int64_t)(k0 + c) * ld_shadow + n0 + ch * 8) = o;
+        }
+        __syncthreads();
+    }
+}
+
 // ------------------------------------------------------------------ Flamingo glue (BASELINE config 4; stand-in oracle: Idefics)
 // ReLU (IdeficsMLP of the Perceiver resampler, perceiver.py:171-187)
 __global__ __launch_bounds__(256) void relu_fwd_kernel(const bf16* __restrict__ x, bf16* __restrict__ y, int64_t nvec) {
@@ -1008,6 +1115,41 @@ extern "C" int afk_adamw_step_t(float* master, float* m, float* v, const void* g
     hipLaunchKernelGGL(adamw_t_kernel, dim3((unsigned)grid), dim3(256), 0, ST, master, m, v, (const bf16*)grad, (bf16*)param, (bf16*)shadow, N, K,
                        ld_shadow, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), grad_scale, gate, hyper);
     AFK_LAUNCH_CHECK("afk_adamw_step_t");
+    return AFK_OK;
+}
+
+// AdamW with bf16 state on a flat range: param / m / v updated in place, every one of them bf16 (include/afk.h)
+extern "C" int afk_adamw16_step(void* m, void* v, const void* grad, void* param, int64_t n, double lr, double beta1, double beta2, double eps,
+                                double weight_decay, int step, float grad_scale, int max_blocks, const int* gate, const float* hyper, void* stream) {
+    AFK_REQUIRE(m && v && grad && param && n > 0 && step >= 1, "afk_adamw16_step: bad args");
+    AFK_REQUIRE(((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)grad % 16 == 0) && ((uintptr_t)param % 16 == 0),
+                "afk_adamw16_step: misaligned buffer");
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);  // double, rounded to fp32 once: torch's bias corrections
+    int grid = ew_grid(afk_cdiv(n, 8), 256);  // max_blocks: the thin-launch rule of afk_adamw_step
+    if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+    hipLaunchKernelGGL(adamw16_kernel, dim3(grid), dim3(256), 0, ST, (bf16*)param, (bf16*)m, (bf16*)v, (const bf16*)grad, n, (float)lr,
+                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale,
+                       gate, hyper);
+    AFK_LAUNCH_CHECK("afk_adamw16_step");
+    return AFK_OK;
+}
+
+extern "C" int afk_adamw16_step_t(void* m, void* v, const void* grad, void* param, void* shadow, int N, int K, int64_t ld_shadow, double lr,
+                                  double beta1, double beta2, double eps, double weight_decay, int step, float grad_scale, int max_blocks,
+                                  const int* gate, const float* hyper, void* stream) {
+    AFK_REQUIRE(m && v && grad && param && shadow && step >= 1, "afk_adamw16_step_t: bad args");
+    AFK_REQUIRE(N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0 && ld_shadow >= N && ld_shadow % 8 == 0, "afk_adamw16_step_t: N=%d, K=%d must be multiples of 64", N, K);
+    AFK_REQUIRE(((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)grad % 16 == 0) && ((uintptr_t)param % 16 == 0) &&
+                    ((uintptr_t)shadow % 16 == 0),
+                "afk_adamw16_step_t: misaligned buffer");
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    int64_t grid = (int64_t)(N / 64) * (K / 64);
+    if (grid > 16384) grid = 16384;
+    if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+    hipLaunchKernelGGL(adamw16_t_kernel, dim3((unsigned)grid), dim3(256), 0, ST, (bf16*)param, (bf16*)m, (bf16*)v, (const bf16*)grad, (bf16*)shadow, N, K,
+                       ld_shadow, (float)lr, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)bc1,
+                       (float)sqrt(bc2), grad_scale, gate, hyper);
+    AFK_LAUNCH_CHECK("afk_adamw16_step_t");
     return AFK_OK;
 }
 

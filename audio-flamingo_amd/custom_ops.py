@@ -322,3 +322,11 @@ def adamw_step(master: Tensor, m: Tensor, v: Tensor, grad: Tensor, param: Tensor
     gate and (lr, bias corrections, clip coefficient) for the HIP-graph-replayed step"""
     ops.adamw_step(master, m, v, grad, param, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, step=step, grad_scale=grad_scale,
                    max_blocks=max_blocks, gate=gate, hyper=hyper)
+
+
+@torch.library.custom_op("afk::adamw16_step", mutates_args=("m", "v", "param"), device_types=_DEV)
+def adamw16_step(m: Tensor, v: Tensor, grad: Tensor, param: Tensor, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                 step: int, grad_scale: float, max_blocks: int, gate: Optional[Tensor] = None, hyper: Optional[Tensor] = None) -> None:
+    """torch.optim.AdamW(fused=True) on a flat range of a bf16 model (bf16 m / v, no fp32 master: 14 B/param); gate / hyper as afk::adamw_step"""
+    ops.adamw16_step(m, v, grad, param, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, step=step, grad_scale=grad_scale,
+                     max_blocks=max_blocks, gate=gate, hyper=hyper)

@@ -754,6 +754,32 @@ def adamw_step_t(master, m, v, grad, param, shadow, N, K, *, lr, beta1, beta2, e
               _p(gate), _p(hyper), _stream())
 
 
+def adamw16_step(m, v, grad, param, *, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, max_blocks=0, gate=None, hyper=None):
+    """AdamW with bf16 state (torch.optim.AdamW(fused=True) on bf16 tensors; 14 B/param): param / m / v are bf16 and updated in place, there is no
+    fp32 master.  gate / hyper / max_blocks as adamw_step."""
+    for t, what in ((m, "adamw16 m"), (v, "adamw16 v"), (grad, "adamw16 grad"), (param, "adamw16 param")):
+        _chk(t, BF16, what)
+        if t.numel() != param.numel():
+            raise AfkError(f"{what}: {t.numel()} elements, param has {param.numel()}")
+    _lib.call("afk_adamw16_step", m.data_ptr(), v.data_ptr(), grad.data_ptr(), param.data_ptr(), param.numel(),
+              float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step), float(grad_scale),
+              int(max_blocks), _p(gate), _p(hyper), _stream())
+
+
+def adamw16_step_t(m, v, grad, param, shadow, N, K, *, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, max_blocks=0, gate=None, hyper=None):
+    """adamw16_step on one 2-D weight [N, K] (flat views of the arena) that also writes shadow [K, ld] = the K-major copy of the updated weight"""
+    for t, what in ((m, "adamw16_t m"), (v, "adamw16_t v"), (grad, "adamw16_t grad"), (param, "adamw16_t param")):
+        _chk(t, BF16, what)
+        if t.numel() != int(N) * int(K):
+            raise AfkError(f"{what}: {t.numel()} elements, [N, K] = [{N}, {K}]")
+    _chk(shadow, BF16, "adamw16_t shadow")
+    if shadow.shape[0] < int(K) or shadow.stride(0) < int(N):
+        raise AfkError(f"adamw16_t shadow: {tuple(shadow.shape)} (row stride {shadow.stride(0)}) cannot hold [K, N] = [{K}, {N}]")
+    _lib.call("afk_adamw16_step_t", m.data_ptr(), v.data_ptr(), grad.data_ptr(), param.data_ptr(), shadow.data_ptr(), int(N), int(K),
+              shadow.stride(0), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step), float(grad_scale), int(max_blocks),
+              _p(gate), _p(hyper), _stream())
+
+
 def sumsq_workspace_floats() -> int:
     return int(_lib.load().afk_sumsq_workspace_floats())
 

@@ -1,6 +1,7 @@
 """Training-loop compatibility layer: run existing fine-tune scripts on the MI355X path.
 
-  * ``AfkAdamW``     - the fused arena optimizer (arena.FusedAdamW: bf16 params + fp32 master / m / v, one launch per decay class)
+  * ``AfkAdamW``     - the fused arena optimizer (arena.FusedAdamW: bf16 params + fp32 master / m / v, one launch per decay class;
+                       ``state_dtype="bf16"``: torch's fused AdamW on a bf16 model - bf16 m / v, no master)
                        behind the ``torch.optim.Optimizer`` interface: ``param_groups`` (LR schedulers write ``lr`` there),
                        ``step()``, ``zero_grad()``, ``state_dict()`` / ``load_state_dict()`` for checkpoint / resume.
   * ``AfkTrainer``   - ``transformers.Trainer`` subclass: builds ``AfkAdamW`` from the TrainingArguments, never wraps the model in
@@ -15,15 +16,15 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .arena import FusedAdamW
+from .arena import FusedAdamW, check_state_dtype
 
 
 class AfkAdamW(torch.optim.Optimizer):
-    def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, state_dtype=None):
         self.arena = model.arena
         params = [p for p in model.parameters() if p.requires_grad]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self.fused = FusedAdamW(self.arena, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.fused = FusedAdamW(self.arena, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, state_dtype=state_dtype)
         self.grad_scale = 1.0  # set to 1/world by a caller that hands over SUMMED data-parallel gradients
         self.gates = None      # data parallel: DataParallelEngine.bucket_gate of the exchange that preceded this step
 
@@ -41,11 +42,21 @@ class AfkAdamW(torch.optim.Optimizer):
 
     def state_dict(self):
         f = self.fused
+        groups = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
+        if f.master is None:   # bf16 state: the weights are the model's bf16 parameters and travel in the model checkpoint
+            return {"state": {"m": f.m, "v": f.v, "t": f.t}, "state_dtype": "bf16", "param_groups": groups}
         return {"state": {"master": f.master, "m": f.m, "v": f.v, "t": f.t},
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+                "param_groups": groups}
 
     def load_state_dict(self, sd):
         f = self.fused
+        check_state_dtype(sd, f.state_dtype, "AfkAdamW.load_state_dict")
+        if f.master is None:   # m / v / t only: the parameters are not written, they come from the model checkpoint
+            f.m.copy_(sd["state"]["m"]), f.v.copy_(sd["state"]["v"])
+            f.t = int(sd["state"]["t"])
+            for g, s in zip(self.param_groups, sd["param_groups"]):
+                g.update(s)
+            return
         f.master.copy_(sd["state"]["master"]), f.m.copy_(sd["state"]["m"]), f.v.copy_(sd["state"]["v"])
         f.t = int(sd["state"]["t"])
         for g, s in zip(self.param_groups, sd["param_groups"]):
@@ -69,6 +80,15 @@ def _trainer_base():
     from transformers import Trainer
 
     return Trainer
+
+
+def _optim_arg(args, key):
+    """`key=value` from TrainingArguments.optim_args ("a=1,b=2", the format TF/trainer.py parses); None when absent"""
+    for item in (getattr(args, "optim_args", None) or "").replace(" ", "").split(","):
+        k, sep, v = item.partition("=")
+        if sep and k == key:
+            return v
+    return None
 
 
 class AfkTrainer(_trainer_base()):
@@ -97,7 +117,7 @@ class AfkTrainer(_trainer_base()):
         if self.optimizer is None:
             a = self.args
             self.optimizer = AfkAdamW(self.model, lr=a.learning_rate, betas=(a.adam_beta1, a.adam_beta2), eps=a.adam_epsilon,
-                                      weight_decay=a.weight_decay)
+                                      weight_decay=a.weight_decay, state_dtype=_optim_arg(a, "state_dtype"))
         return self.optimizer
 
     def _engine(self):

@@ -432,6 +432,18 @@ int afk_adamw_step(float* master, float* m, float* v, const void* grad, void* pa
 int afk_adamw_step_t(float* master, float* m, float* v, const void* grad, void* param, void* shadow, int N, int K, int64_t ld_shadow, float lr,
                      float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, int max_blocks, const int* gate,
                      const float* hyper, void* stream);
+/* AdamW with bf16 optimizer state (14 B/param): torch.optim.AdamW(fused=True) on a bf16 model (TORCH/optim/adamw.py, fused path -> torch._fused_adamw_).
+ * The bf16 parameters are the only copy of the weights (no fp32 master) and m / v are bf16 arrays of the same length.  Per element: widen p, m, v, g to
+ * fp32; g *= grad_scale [* hyper[3]]; p -= lr*wd*p; m += (1-beta1)*(g-m); v = beta2*v + (1-beta2)*g*g; p -= (lr/bc1)*m / (sqrt(v)/sqrt(bc2) + eps); round
+ * p, m, v to bf16 once, on the store.  gate / hyper / max_blocks / step as afk_adamw_step; every buffer 16-byte aligned.  afk_adamw16_step_t is to it what
+ * afk_adamw_step_t is to afk_adamw_step: one 2-D weight [N, K] (multiples of 64), bit-identical p / m / v, shadow == transpose(param).
+ * The five hyper-parameters are double, as in torch._fused_adamw_: 1 - beta1, 1 - beta2 and the bias corrections are taken in double and rounded to fp32
+ * once (1.f - 0.999f is 1.3e-5 away from 0.001; with bf16 parameters that error shows wherever p and the update nearly cancel). */
+int afk_adamw16_step(void* m, void* v, const void* grad, void* param, int64_t n, double lr, double beta1, double beta2, double eps,
+                     double weight_decay, int step, float grad_scale, int max_blocks, const int* gate, const float* hyper, void* stream);
+int afk_adamw16_step_t(void* m, void* v, const void* grad, void* param, void* shadow, int N, int K, int64_t ld_shadow, double lr,
+                       double beta1, double beta2, double eps, double weight_decay, int step, float grad_scale, int max_blocks,
+                       const int* gate, const float* hyper, void* stream);
 int afk_set_f32(float* dst, int n, float a, float b, float c, float d, void* stream);
 /* global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, TORCH/nn/utils/clip_grad.py; HF Trainer default max_grad_norm = 1.0,
  * TF/trainer.py): acc[0] += sum of squares of a bf16 range (skipped when *gate == 0; gate may be NULL), deterministic two-stage fold;

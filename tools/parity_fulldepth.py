@@ -354,7 +354,7 @@ def _leg(dev, cfg, variant, batch, micro_fp32, long_windows, lr, enc_layers, dec
     m = Mine(cfg, device=dev, init_seed=0)
     m.load_state_dict(sd)
     del sd
-    opt = FusedAdamW(m.arena, lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0) if with_adamw else None
+    opt = FusedAdamW(m.arena, lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, state_dtype="fp32") if with_adamw else None  # the check reads the fp32 master
     frontend = LogMelFrontend(dev)
     res["logmel_max_abs_diff_vs_reference_frontend"] = float((frontend(waves, out_dtype=torch.float32) - feats_ref).abs().max())
     if long_windows:   # forward only, BEFORE the optimizer moves the weights
