@@ -1,0 +1,363 @@
+// Token sampling on the device for the decode step (generate(do_sample=True)): temperature -> top-k -> top-p -> draw, one launch, no host state - the step
+// can be captured into a HIP graph like the greedy one.  Oracle: TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper
+// (transformers/generation/logits_process.py) and the multinomial draw of GenerationMixin._sample (transformers/generation/utils.py).
+//
+// One 1024-thread block per row of fp32 logits (the 608 KB row of the AF3 vocabulary stays in L2 across the passes).  Floats map to order-preserving
+// 32-bit keys; thresholds come from MSB-first radix selection in 11 / 11 / 10-bit passes over LDS histograms, never from a sort:
+//   top-k   histogram of COUNTS,  walked from the top:    the key of the min(top_k, V)-th largest value (ties at the threshold all stay, as `logits < kth` keeps them)
+//   top-p   histogram of MASSES over the K-set, walked from the bottom: the smallest key whose inclusive cumulative mass exceeds (1 - top_p) x the K-set's mass
+//           (the reference's ascending cumsum including the token itself; a class of equal values stays or goes as a whole)
+//   draw    masses of the kept set in token-id order: per-granule sums, one block scan, one wave walks the granule that holds u x total
+// Every mass is the 64-bit fixed-point integer round(exp(z - max) * 2^40), at least 1 where the exponential is positive: integer sums do not depend on the
+// order of the LDS atomics or on the launch geometry, so the token is a pure function of (logits, parameters, u).  The quantisation is 2^-40 of the largest
+// term per token (1.4e-7 of the total over 152 064 tokens), far below fp32 exp's own error.
+#include "common.h"
+#include "../../include/afk.h"
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr int NT = 1024, NW = NT / 64;
+constexpr int NB = 2048;        // bins of an 11-bit pass (the last pass has 1024)
+constexpr int NG_MAX = 4096;    // granule sums of the draw held in LDS: four per thread
+constexpr float MASS_ONE = 1099511627776.f;   // 2^40
+
+struct SampleArgs {
+    const float* logits; int64_t ld; int V; float T; int top_k; float top_p; const float* u; uint32_t key0, key1; const int* step_base; int step_off;
+    long long* next_token; float* probs; int64_t ld_probs; int* kept; long long* tokens_out; int tok_off; int* state; const bf16* emb; int64_t ld_emb; int H;
+    bf16* x_out;
+};
+struct Sel { int bin; u64 excl, total, target; };
+
+// z = logits / T (fp32 division as the warper's `scores / temperature`; T == 1: untouched); NaN counts as -inf, -0 as +0 (one class with +0)
+__device__ __forceinline__ float zval(float x, float T, bool div) {
+    float z = div ? x / T : x;
+    if (!(z == z)) z = -INFINITY;
+    if (z == 0.f) z = 0.f;
+    return z;
+}
+// order-preserving key: a < b  <=>  key(a) < key(b)
+__device__ __forceinline__ uint32_t key_of(float z) {
+    const uint32_t b = __float_as_uint(z);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ u64 mass_of(float z, float zmax) {
+    const float e = expf(z - zmax);
+    const u64 m = __float2ull_rn(e * MASS_ONE);
+    return (e > 0.f && m == 0) ? 1 : m;   // a kept token with a positive probability can be drawn (u = 0 answers the lowest kept id)
+}
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ u64 wave_scan_u64(u64 v, int lane) {   // inclusive
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 n = __shfl_up(v, o, 64);
+        if (lane >= o) v += n;
+    }
+    return v;
+}
+// inclusive scan over the block's threads in thread order; total = the block's sum
+__device__ __forceinline__ u64 block_scan_incl(u64 v, u64* wtot, u64& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    v = wave_scan_u64(v, lane);
+    __syncthreads();
+    if (lane == 63) wtot[w] = v;
+    __syncthreads();
+    u64 base = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const u64 x = wtot[i];
+        if (i < w) base += x;
+        tot += x;
+    }
+    total = tot;
+    return v + base;
+}
+// the first bin, walking h[0 .. nb) upwards (or downwards: desc), whose inclusive running sum exceeds `target` (use_frac: target = frac x the sum of all bins);
+// sel = {bin, the running sum in front of it, the sum of all bins, target}.  nb = 1024 or 2048.  Ends with a barrier.
+template <typename HT>
+__device__ __forceinline__ void select_bin(const HT* h, int nb, bool desc, bool use_frac, double frac, u64 target, u64* wtot, Sel* sel) {
+    const int t = threadIdx.x, per = nb >> 10;
+    u64 a[2] = {0, 0};
+    for (int j = 0; j < per; ++j) {
+        const int p = t * per + j;
+        a[j] = h[desc ? nb - 1 - p : p];
+    }
+    if (t == 0) { sel->bin = desc ? 0 : nb - 1; sel->excl = 0; sel->total = 0; sel->target = 0; }   // never left unset (a bin is always found: see the callers)
+    const u64 local = a[0] + a[1];
+    u64 total;
+    const u64 incl = block_scan_incl(local, wtot, total), excl = incl - local;
+    if (use_frac) {
+        target = (u64)(frac * (double)total);
+        if (total && target >= total) target = total - 1;
+    }
+    if (excl <= target && target < incl) {   // one thread
+        const int j = (target < excl + a[0]) ? 0 : 1;
+        const int p = t * per + j;
+        sel->bin = desc ? nb - 1 - p : p;
+        sel->excl = excl + (j ? a[0] : 0);
+        sel->total = total;
+        sel->target = target;
+    }
+    __syncthreads();
+}
+
+// f(i, logits[i]) for the ids i = t, t + 1024, ... of a row, eight loads in flight per thread (one load per round trip: 197 / 297 us per launch for top-k /
+// top-k + top-p at V = 152 064, eight: 183 / 259 - the passes are bound by the one CU's vector ALU, profiles/decode_sampling.md)
+constexpr int LU = 8;
+template <typename F>
+__device__ __forceinline__ void for_each_logit(const float* __restrict__ row, int V, int t, F&& f) {
+    int base = 0;
+    for (; base + LU * NT <= V; base += LU * NT) {
+        float x[LU];
+#pragma unroll
+        for (int u = 0; u < LU; ++u) x[u] = row[base + u * NT + t];
+#pragma unroll
+        for (int u = 0; u < LU; ++u) f(base + u * NT + t, x[u]);
+    }
+    float x[LU];
+#pragma unroll
+    for (int u = 0; u < LU; ++u) {
+        const int i = base + u * NT + t;
+        x[u] = i < V ? row[i] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < LU; ++u) {
+        const int i = base + u * NT + t;
+        if (i < V) f(i, x[u]);
+    }
+}
+
+// Philox4x32-10 (Salmon et al., SC'11), word 0 of the output block
+__device__ __forceinline__ uint32_t philox4x32_10_w0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0, h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+__global__ __launch_bounds__(NT) void decode_sample_kernel(SampleArgs a) {
+    __shared__ u64 hmass[NB];
+    __shared__ unsigned int hcnt[NB];
+    __shared__ u64 gsum[NG_MAX];
+    __shared__ u64 wtot[NW];
+    __shared__ float wmax_s[NW];
+    __shared__ int winf_s[NW], wcnt_s[NW];
+    __shared__ Sel sel;
+    __shared__ int s_tok, s_step;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, b = blockIdx.x, V = a.V;
+    const float* __restrict__ row = a.logits + (int64_t)b * a.ld;
+    const float T = a.T;
+    const bool div = T != 1.f;
+    const int kk = (a.top_k > 0 && a.top_k < V) ? a.top_k : 0;   // 0: every token is in the K-set
+    const bool use_p = a.top_p < 1.f;
+    if (t == 0) s_step = (a.step_base ? *a.step_base : 0) + a.step_off;   // read before the bookkeeping below advances the state it may live in
+
+    // ---- pass A: row maximum, lowest +inf, and the first count histogram
+    for (int i = t; i < NB; i += NT) hcnt[i] = 0;
+    __syncthreads();
+    float zmax = -INFINITY;
+    int iinf = 0x7fffffff;
+    for_each_logit(row, V, t, [&](int i, float x) {
+        const float z = zval(x, T, div);
+        zmax = fmaxf(zmax, z);
+        if (z == INFINITY) iinf = min(iinf, i);
+        if (kk) atomicAdd(&hcnt[key_of(z) >> 21], 1u);
+    });
+    zmax = wave_max(zmax);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) iinf = min(iinf, __shfl_xor(iinf, o, 64));
+    if (lane == 0) { wmax_s[w] = zmax; winf_s[w] = iinf; }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NW; ++i) { zmax = fmaxf(zmax, wmax_s[i]); iinf = min(iinf, winf_s[i]); }
+    const int mode = iinf != 0x7fffffff ? 1 : (zmax == -INFINITY ? 2 : 0);   // 1: a +inf wins (lowest index); 2: no finite logit -> 0; both as torch.argmax
+
+    int tok = mode == 1 ? iinf : 0, kept_n = mode == 1 ? 1 : 0;
+    uint32_t thr = 0;
+    float inv_tot = 0.f;
+    if (mode == 0) {
+        // ---- top-k: key of the kk-th largest value
+        uint32_t kth = 0;
+        if (kk) {
+            uint32_t pfx = 0;
+            u64 rem = (u64)(kk - 1);
+            for (int p = 0; p < 3; ++p) {
+                const int sh = p == 0 ? 21 : p == 1 ? 10 : 0, bits = p == 2 ? 10 : 11, nb = 1 << bits;
+                if (p > 0) {
+                    for (int i = t; i < nb; i += NT) hcnt[i] = 0;
+                    __syncthreads();
+                    for_each_logit(row, V, t, [&](int, float x) {
+                        const uint32_t key = key_of(zval(x, T, div));
+                        if ((key >> (sh + bits)) == pfx) atomicAdd(&hcnt[(key >> sh) & (nb - 1)], 1u);
+                    });
+                    __syncthreads();
+                }
+                select_bin(hcnt, nb, true, false, 0.0, rem, wtot, &sel);   // the bins hold at least rem + 1 elements: V >= kk, then the chosen bin's count
+                pfx = (pfx << bits) | (uint32_t)sel.bin;
+                rem -= sel.excl;
+            }
+            kth = pfx;
+        }
+        thr = kth;
+        // ---- top-p over the K-set: the smallest key whose inclusive cumulative mass exceeds (1 - top_p) of the K-set's mass
+        if (use_p) {
+            uint32_t pfx = 0;
+            u64 rem = 0;
+            for (int p = 0; p < 3; ++p) {
+                const int sh = p == 0 ? 21 : p == 1 ? 10 : 0, bits = p == 2 ? 10 : 11, nb = 1 << bits;
+                for (int i = t; i < nb; i += NT) hmass[i] = 0;
+                __syncthreads();
+                for_each_logit(row, V, t, [&](int, float x) {
+                    const float z = zval(x, T, div);
+                    const uint32_t key = key_of(z);
+                    if (key >= kth && (p == 0 || (key >> (sh + bits)) == pfx)) atomicAdd(&hmass[(key >> sh) & (nb - 1)], mass_of(z, zmax));
+                });
+                __syncthreads();
+                // the maximum is in the K-set with mass 2^40, and (1 - top_p) < 1: the target is below the total in every pass
+                select_bin(hmass, nb, false, p == 0, 1.0 - (double)a.top_p, rem, wtot, &sel);
+                pfx = (pfx << bits) | (uint32_t)sel.bin;
+                rem = sel.target - sel.excl;
+            }
+            thr = pfx;   // >= kth: only K-set keys were counted
+        }
+        // ---- draw: masses of the kept set in token-id order
+        float u;
+        if (a.u) {
+            u = a.u[b];
+        } else {
+            u = (float)(philox4x32_10_w0((uint32_t)s_step, (uint32_t)b, 0u, 0u, a.key0, a.key1) >> 8) * 5.9604644775390625e-8f;
+        }
+        if (!(u >= 0.f)) u = 0.f;
+        if (u >= 1.f) u = 1.f - 5.9604644775390625e-8f;
+        const int m = (V + 64 * NG_MAX - 1) / (64 * NG_MAX), gran = 64 * m, ngran = (V + gran - 1) / gran;   // granule = 64 m consecutive ids, at most NG_MAX of them
+        int cnt = 0;
+        for (int g0 = w; g0 < ngran; g0 += NW * LU) {   // LU granules of a wave per round trip (granules g0, g0 + 16, ...)
+            u64 s[LU];
+#pragma unroll
+            for (int q = 0; q < LU; ++q) s[q] = 0;
+            for (int j = 0; j < m; ++j) {
+                float x[LU];
+#pragma unroll
+                for (int q = 0; q < LU; ++q) {
+                    const int g = g0 + q * NW, i = g * gran + j * 64 + lane;
+                    x[q] = (g < ngran && i < V) ? row[i] : -INFINITY;   // -inf is never kept
+                }
+#pragma unroll
+                for (int q = 0; q < LU; ++q) {
+                    const float z = zval(x[q], T, div);
+                    if (key_of(z) >= thr && z > -INFINITY) { s[q] += mass_of(z, zmax); ++cnt; }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < LU; ++q) {
+                const u64 sum = wave_sum_u64(s[q]);
+                if (lane == 0 && g0 + q * NW < ngran) gsum[g0 + q * NW] = sum;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+        if (lane == 0) wcnt_s[w] = cnt;
+        __syncthreads();
+        if (t == 0) { sel.bin = 0; sel.excl = 0; }   // the barriers of the scan below order this before the finder's write
+        kept_n = 0;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) kept_n += wcnt_s[i];
+        u64 a4[4], local = 0, total;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int g = 4 * t + j;
+            a4[j] = g < ngran ? gsum[g] : 0;
+            local += a4[j];
+        }
+        const u64 incl = block_scan_incl(local, wtot, total), excl = incl - local;
+        u64 target = (u64)((double)u * (double)total);   // total >= 2^40 (the maximum is kept), u < 1
+        if (target >= total) target = total - 1;
+        if (excl <= target && target < incl) {
+            u64 e = excl;
+            for (int j = 0; j < 4; ++j) {
+                if (target < e + a4[j]) { sel.bin = 4 * t + j; sel.excl = e; break; }
+                e += a4[j];
+            }
+        }
+        __syncthreads();
+        if (w == 0) {   // one wave walks the granule that holds the target
+            const int g = sel.bin;
+            u64 base = sel.excl;
+            int found = -1;
+            for (int j = 0; j < m && found < 0; ++j) {
+                const int i = g * gran + j * 64 + lane;
+                u64 v = 0;
+                if (i < V) {
+                    const float z = zval(row[i], T, div);
+                    if (key_of(z) >= thr && z > -INFINITY) v = mass_of(z, zmax);
+                }
+                const u64 sc = wave_scan_u64(v, lane);
+                const u64 hit = __ballot(base + sc > target);
+                if (hit) found = g * gran + j * 64 + (int)__ffsll((long long)hit) - 1;
+                base += __shfl(sc, 63, 64);
+            }
+            if (lane == 0) s_tok = found < 0 ? 0 : found;
+        }
+        __syncthreads();
+        tok = s_tok;
+        inv_tot = 1.f / (float)((double)total * (1.0 / (double)MASS_ONE));
+    }
+
+    // ---- outputs
+    if (a.probs) {
+        float* pr = a.probs + (int64_t)b * a.ld_probs;
+        for_each_logit(row, V, t, [&](int i, float x) {
+            float r = 0.f;
+            if (mode == 0) {
+                const float z = zval(x, T, div);
+                if (key_of(z) >= thr && z > -INFINITY) r = expf(z - zmax) * inv_tot;
+            } else if (mode == 1) {
+                r = i == tok ? 1.f : 0.f;
+            }
+            pr[i] = r;
+        });
+    }
+    if (t == 0) {
+        a.next_token[b] = tok;
+        if (a.kept) a.kept[b] = kept_n;
+        if (a.state) {   // the bookkeeping block of decode_select_greedy_kernel (one sequence)
+            if (a.tokens_out) a.tokens_out[a.state[2] + a.tok_off] = tok;
+            a.state[1] += 1;   // key-range end
+            a.state[2] += 1;   // cache slot of the next token
+            a.state[3] += 1;   // its position
+        }
+    }
+    if (a.state) {
+        const bf16* erow = a.emb + (int64_t)tok * a.ld_emb;
+        for (int k = t * 4; k < a.H; k += 4 * NT) *(bf16x4*)(a.x_out + k) = *(const bf16x4*)(erow + k);
+    }
+}
+
+}  // namespace
+
+#define ST ((hipStream_t)stream)
+
+extern "C" int afk_decode_sample(const float* logits, int64_t ld_logits, int B, int V, float temperature, int top_k, float top_p, const float* u, int64_t seed,
+                                 const int* step_base, int step_off, int64_t* next_token, float* probs_out, int64_t ld_probs, int* kept_out, int64_t* tokens_out,
+                                 int tok_off, int* state, const void* emb, int64_t ld_emb, int H, void* x_out, void* stream) {
+    AFK_REQUIRE(logits && next_token, "afk_decode_sample: null pointer (logits, next_token)");
+    AFK_REQUIRE(B >= 1 && V >= 1 && V <= AFK_SAMPLE_MAX_V && ld_logits >= V && (!probs_out || ld_probs >= V),
+                "afk_decode_sample: unsupported shape (B >= 1, 1 <= V <= %d, row strides >= V)", AFK_SAMPLE_MAX_V);
+    AFK_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "afk_decode_sample: temperature %g (finite, temperature > 0)", (double)temperature);
+    AFK_REQUIRE(top_p > 0.f, "afk_decode_sample: top_p %g (top_p > 0; top_p >= 1 switches the filter off)", (double)top_p);
+    AFK_REQUIRE(!state || (B == 1 && emb && x_out && H > 0 && H % 4 == 0 && ld_emb % 4 == 0),
+                "afk_decode_sample: the bookkeeping block (state) needs B == 1, emb, x_out and H %% 4 == 0");
+    AFK_REQUIRE(state || !tokens_out, "afk_decode_sample: tokens_out is indexed by state[2]: null pointer (state)");
+    SampleArgs a = {logits, ld_logits, V, temperature, top_k, top_p, u, (uint32_t)((uint64_t)seed & 0xffffffffu), (uint32_t)((uint64_t)seed >> 32), step_base, step_off,
+                    (long long*)next_token, probs_out, ld_probs, kept_out, (long long*)tokens_out, tok_off, state, (const bf16*)emb, ld_emb, H, (bf16*)x_out};
+    hipLaunchKernelGGL(decode_sample_kernel, dim3(B), dim3(NT), 0, ST, a);
+    AFK_LAUNCH_CHECK("afk_decode_sample");
+    return AFK_OK;
+}

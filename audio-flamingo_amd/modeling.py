@@ -22,7 +22,8 @@ Deviations from the oracle surface (documented, not silent):
   * ``forward(use_cache=True)`` / ``forward(past_key_values=cache)``: the reference's cache protocol for inference (prefill returns an
     ``AfkKVCache``, later calls append one or several tokens); same kernels and cache layout as ``generate``;
   * ``generate``: prefill fills a KV cache, each new token is one HIP-graph replay; greedy by default, ``do_sample=True`` with
-    ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` (the reference's logits-warper order), or ``num_beams > 1`` (beam search with the
+    ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` (the reference's logits-warper order, drawn on the device by ``afk_decode_sample`` inside the
+    replayed step: the ids are a function of the seed, not of torch's generator stream; top-p keeps a class of equal logits whole), or ``num_beams > 1`` (beam search with the
     reference's scoring); ``generation_config`` supplies defaults; constrained / assisted decoding and custom logits processors are not built;
   * ``attention_mask`` rows must be one contiguous run of ones (left padding - the reference processor's default -, right padding, or
     both); masks with holes raise.  Hidden states of padded positions are zeros-attended garbage in both implementations and are
@@ -1020,6 +1021,13 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             wd = A("mlp.down_proj.weight").data
             x = torch.empty_like(x2)
             _lib.call("afk_decode_chain_linear_residual", act.data_ptr(), wd.data_ptr(), wd.stride(0), H, I, x2.data_ptr(), x.data_ptr(), st)
+        if greedy is not None and greedy.get("sampling"):   # sampled: the lm_head launch writes the fp32 logits, the sample launch draws and does the bookkeeping
+            g = greedy
+            _lib.call("afk_decode_chain_lm_head", x.data_ptr(), a[lm + "norm.weight"].data.data_ptr(), eps, head.data_ptr(), head.stride(0), head.shape[0], H,
+                      g["logits"].data_ptr(), None, None, st)
+            self._sample_token(g["logits"], g["sampling"], step_base=g["cur"], step_off=g["tok_off"], out=g["nxt"], tokens_out=g["tok_buf"], tok_off=g["tok_off"],
+                               state=g["state"], emb=g["emb"], x_out=g["x0"])
+            return None
         if greedy is not None:   # generate()'s state dict: the lm_head launch leaves (max, argmax) per eight rows, the select launch does everything up to the next step
             g = greedy
             _lib.call("afk_decode_chain_lm_head", x.data_ptr(), a[lm + "norm.weight"].data.data_ptr(), eps, head.data_ptr(), head.stride(0), head.shape[0], H,
@@ -1177,11 +1185,14 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         return ns
 
     def _decode_step(self, st):
-        """one greedy decode step on static buffers (everything position-dependent lives on the device): HIP-graph capturable"""
-        if "x0" in st:   # greedy, one sequence: 5 launches per layer + lm_head + ONE launch for argmax / token / positions / the next embedding row
+        """one greedy or sampled decode step on static buffers (everything position-dependent lives on the device): HIP-graph capturable"""
+        if "x0" in st:   # one sequence: 5 launches per layer + lm_head + ONE launch for argmax or the draw / token / positions / the next embedding row
             self._decode_layers_chain(st["x0"], st["cache"], st["pos1"], st["kr1"], st["cur"], aws=st["aws"], head=st["head"], greedy=st)
             return
-        st["nxt"].copy_(self._select_token(self._decode_logits(st), st.get("sampling")))
+        if st.get("sampling"):   # the token being generated is number cur + 1 - S0: the draw's counter lives on the device and advances with the step
+            self._sample_token(self._decode_logits(st), st["sampling"], step_base=st["cur"], step_off=st["tok_off"], out=st["nxt"])
+        else:
+            st["nxt"].copy_(self._select_token(self._decode_logits(st)))
         (st["advance"] if "advance" in st else st["cur"]).add_(1)   # single sequence: cur, position and the key-range end live in one tensor (generate())
 
     @torch.no_grad()
@@ -1305,12 +1316,21 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             logits = logits.masked_fill(drop.scatter(-1, si, drop), float("-inf"))
         return torch.multinomial(logits.softmax(-1), 1, generator=gen).squeeze(-1)
 
+    @staticmethod
+    def _sample_token(logits, sampling, **kw):
+        """the sampling chain of _select_token on the device, in one launch and with no host state (ops.decode_sample): temperature -> top-k -> top-p -> the
+        draw from a counter-based generator keyed by sampling["seed"]; kw: the draw's counter (step_base / step_off) and the outputs"""
+        if logits.dtype != torch.float32 or logits.stride(-1) != 1:
+            logits = logits.float().contiguous()
+        return ops.decode_sample(logits, temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"], seed=sampling["seed"], **kw)
+
     @torch.no_grad()
     def generate(self, input_ids, input_features=None, input_features_mask=None, attention_mask=None, max_new_tokens=20,
                  do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, eos_token_id=None, pad_token_id=None, use_cache=True,
                  use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, **kwargs):
         """Greedy decoding, sampling or beam search (GenerationMixin.generate, transformers/generation/utils.py; do_sample with temperature /
-        top_k / top_p as its logits warpers apply them; seed -> a device generator, so runs are reproducible; num_beams > 1: beam search with the
+        top_k / top_p as its logits warpers apply them, drawn on the device by afk_decode_sample from a counter-based generator: seed (64 bits; None: from
+        torch.seed()) and the index of the token are all the state there is, so a seed gives the same ids in eager, graph-replayed and hook-driven loops; num_beams > 1: beam search with the
         reference's scoring - accumulated log-probabilities, finished hypotheses ranked by sum / length^length_penalty, its early-stop
         heuristic).  generation_config (a transformers.GenerationConfig or anything with the same attributes) supplies defaults for the
         arguments left at theirs, as GenerationMixin merges them.  Cache handling as
@@ -1347,11 +1367,9 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         if hooks and (num_beams > 1 or not use_cache):
             raise AfkError("generate(logits_processor / stopping_criteria / streamer): greedy or sampled decoding on the KV cache only")
         sampling = None
-        if do_sample:
-            gen = torch.Generator(device=self.device_)
-            gen.manual_seed(int(seed) if seed is not None else int(torch.seed() % (2 ** 31)))
-            sampling = dict(temperature=float(temperature), top_k=int(top_k or 0), top_p=None if top_p is None else float(top_p), generator=gen)
-            use_graph = False  # the sampler draws from a host-side generator object: eager steps
+        if do_sample and int(top_k or 0) != 1:   # top_k == 1 is greedy selection (and keeps the no-logits path)
+            sampling = dict(temperature=float(temperature) if temperature else 1.0, top_k=int(top_k or 0), top_p=1.0 if top_p is None else float(top_p),
+                            seed=(int(seed) if seed is not None else int(torch.seed())) & (2 ** 64 - 1))
         ids = input_ids.to(self.device_)
         if not use_cache:
             if do_sample:
@@ -1386,16 +1404,20 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         if procs:
             first_logits = procs(ids, first_logits)
         st = {"cache": (Kc, Vt), "lo": lo, "head": self.arena["lm_head.weight"].data, "emb": self.arena[self._lm + "embed_tokens.weight"].data,
-              "cur": torch.full((1,), S0, device=dev, dtype=torch.int32), "sampling": sampling, "nxt": self._select_token(first_logits, sampling)}
+              "cur": torch.full((1,), S0, device=dev, dtype=torch.int32), "sampling": sampling, "tok_off": 1 - S0,
+              "nxt": self._sample_token(first_logits, sampling) if sampling else self._select_token(first_logits)}   # the first token is draw 0
         if B == 1:   # one device tensor [lo, key-range end, cache slot, position] -> the views the kernels read; one add per step moves the last three
             state = torch.cat([lo, torch.tensor([S0 + 1, S0], device=dev, dtype=torch.int32), S0 - lo]).contiguous()
             st.update(cur=state[2:3], kr1=state[0:2], pos1=state[3:4], advance=state[1:4], state=state)
-            if sampling is None and not hooks and self._chain_ok(1) and st["head"].shape[0] % 8 == 0:   # greedy: token selection and step bookkeeping stay on the device
+            if not hooks and self._chain_ok(1) and st["head"].shape[0] % 8 == 0:   # token selection (argmax or the draw) and step bookkeeping stay on the device
                 tok_buf = torch.zeros(max_new_tokens, device=dev, dtype=torch.int64)
                 tok_buf[0] = st["nxt"][0]
-                st.update(x0=st["emb"].index_select(0, st["nxt"]).contiguous(), aws=self._decode_attn_workspace(dev, Vt.shape[4]), tok_buf=tok_buf, tok_off=1 - S0,
-                          part_val=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.float32),
-                          part_idx=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.int32))
+                st.update(x0=st["emb"].index_select(0, st["nxt"]).contiguous(), aws=self._decode_attn_workspace(dev, Vt.shape[4]), tok_buf=tok_buf)
+                if sampling:
+                    st.update(logits=torch.empty((1, st["head"].shape[0]), device=dev, dtype=torch.float32))
+                else:
+                    st.update(part_val=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.float32),
+                              part_idx=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.int32))
         if hooks:
             return self._generate_with_hooks(ids, st, first_logits, int(max_new_tokens), procs, criteria, streamer, eos_token_id, pad_token_id)
         on_device = "x0" in st
@@ -1431,7 +1453,8 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         """GenerationMixin._sample's loop with its per-step callbacks (transformers/generation/utils.py:2730-2830): scores = logits_processor(input_ids,
         logits); token = argmax / multinomial; finished rows emit pad_token_id; streamer.put(tokens) (the prompt first, streamer.end() at the end);
         a row finishes on EOS or when stopping_criteria(input_ids, scores) says so.  Host code runs between the steps, so they are enqueued eagerly
-        (no HIP graph, token selection through torch) - the decode kernels are the ones of the graph path."""
+        (no HIP graph) - the decode kernels are the ones of the graph path, and a sampled token is draw t of afk_decode_sample on the PROCESSED scores (a
+        token a processor set to -inf is never drawn), the same draw the graph path makes for token t."""
         B = ids.shape[0]
         dev = ids.device
         eos = None if eos_token_id is None else torch.as_tensor(eos_token_id, device=dev).reshape(-1)
@@ -1446,7 +1469,7 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
                 (st["advance"] if "advance" in st else st["cur"]).add_(1)
                 if procs:
                     logits = procs(seq, logits)
-            tok = self._select_token(logits, st.get("sampling"))
+            tok = self._sample_token(logits, st["sampling"], step_off=t) if st.get("sampling") else self._select_token(logits)
             tok = torch.where(done, torch.full_like(tok, pad), tok)
             seq = torch.cat([seq, tok[:, None]], dim=1)
             if streamer is not None:

@@ -718,6 +718,45 @@ def scatter_rows(src, rows, M):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- token sampling
+def decode_sample(logits, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, u=None, step_base=None, step_off=0, out=None, probs_out=None, kept_out=None,
+                  tokens_out=None, tok_off=0, state=None, emb=None, x_out=None):
+    """next_token [B] (int64) drawn from the fp32 logits [B, V]: temperature -> top-k -> top-p -> draw in one launch (afk_decode_sample; the contract is in
+    include/afk.h).  u [B] fp32 on the device supplies the uniforms; without it they come from Philox4x32-10 keyed by the 64-bit `seed`, counter
+    (*step_base + step_off, row).  probs_out [B, V] fp32 / kept_out [B] int32: the distribution drawn from and the size of its support.  state (int32
+    [start, end, slot, position], B == 1) with emb / x_out (and tokens_out / tok_off): the step bookkeeping of afk_decode_select_greedy in the same launch."""
+    _chk(logits, torch.float32, "decode_sample logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise AfkError(f"decode_sample logits: [B, V] with unit column stride, got {tuple(logits.shape)} strides {logits.stride()}")
+    B, V = logits.shape
+    if out is None:
+        out = torch.empty(B, device=logits.device, dtype=torch.int64)
+    for t_, dt, n, name in ((out, torch.int64, B, "out"), (u, torch.float32, B, "u"), (kept_out, torch.int32, B, "kept_out"), (step_base, torch.int32, 1, "step_base"),
+                            (tokens_out, torch.int64, 1, "tokens_out"), (state, torch.int32, 4, "state")):
+        if t_ is not None:
+            _chk(t_, dt, f"decode_sample {name}")
+            if t_.numel() < n or not t_.is_contiguous():
+                raise AfkError(f"decode_sample {name}: a contiguous tensor of at least {n} elements, got {tuple(t_.shape)}")
+    if probs_out is not None:
+        _chk(probs_out, torch.float32, "decode_sample probs_out")
+        if probs_out.shape != logits.shape or probs_out.stride(1) != 1:
+            raise AfkError(f"decode_sample probs_out: {tuple(logits.shape)} with unit column stride, got {tuple(probs_out.shape)}")
+    H = 0
+    if state is not None:
+        if emb is None or x_out is None:
+            raise AfkError("decode_sample: state needs emb and x_out (the embedding row of the token is the next step's input)")
+        _chk(emb, BF16, "decode_sample emb"), _chk(x_out, BF16, "decode_sample x_out")
+        H = emb.shape[1]
+        if x_out.numel() < H or not x_out.is_contiguous() or V > emb.shape[0]:
+            raise AfkError(f"decode_sample: x_out holds {x_out.numel()} elements, emb is {tuple(emb.shape)} for V = {V}")
+    seed = int(seed) & (2 ** 64 - 1)
+    _lib.call("afk_decode_sample", logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0), float(top_p), _p(u),
+              seed - 2 ** 64 if seed >= 2 ** 63 else seed, _p(step_base), int(step_off), out.data_ptr(), _p(probs_out),
+              probs_out.stride(0) if probs_out is not None else 0, _p(kept_out), _p(tokens_out), int(tok_off), _p(state), _p(emb),
+              emb.stride(0) if emb is not None else 0, H, _p(x_out), _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- loss
 def count_valid(labels):
     out = torch.empty(1, device=labels.device, dtype=torch.float32)

@@ -365,6 +365,28 @@ int afk_decode_chain_lm_head(const void* x, const void* norm_w, float eps, const
  * the last three += 1; x_out[H] = emb[token][:H] (the embedding lookup of the next step, Qwen2Model.embed_tokens). */
 int afk_decode_select_greedy(const float* part_val, const int* part_idx, int nparts, int64_t* next_token, int64_t* tokens_out, int tok_off, int* state,
                              const void* emb, int64_t ld_emb, int H, void* x_out, void* stream);
+/* Sampled token selection on the device (csrc/decode_sample.hip), one launch for B rows of fp32 logits [B][V] (row stride ld_logits; any V >= 1, any B >= 1): what
+ * TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper (transformers/generation/logits_process.py) and the multinomial draw of GenerationMixin._sample
+ * (transformers/generation/utils.py) do per step, with no host state - enqueue-only, no allocation, capturable.  Per row:
+ *   1. z = logits / temperature in fp32 (temperature == 1: untouched); NaN counts as -inf.
+ *   2. K-set: top_k > 0 keeps { i : z_i >= the min(top_k, V)-th largest z } - ties at the threshold all stay, as the warper's `scores < kth` mask keeps them; else all.
+ *   3. P-set: top_p < 1 keeps token i of the K-set iff sum over { j in K-set : z_j <= z_i } of softmax_K(z)_j > 1 - top_p (the warper's ascending cumulative sum
+ *      including the token itself).  A class of equal values stays or goes as a whole (the warper splits it by its sort's arbitrary order - the one deviation, and a
+ *      deterministic one); the class of the row maximum always stays.
+ *   4. r = softmax(z) over the kept set, 0 elsewhere.
+ *   5. token = the smallest kept id i (ascending token ids) with sum_{j <= i} r_j > u, u in [0, 1).
+ *   6. a row with a +inf answers the lowest id holding one, a row with no finite logit answers 0 (as afk_decode_select_greedy and torch.argmax do).
+ * u: device array u[B], or null = Philox4x32-10 with key (seed low word, seed high word) and counter (t, row, 0, 0), t = *step_base + step_off = the index of the token
+ * being generated (step_base: device int32, null = 0; with step_base = &state[2] and step_off = tok_off it is the tokens_out index and advances by itself under graph
+ * replay); u = (word0 >> 8) * 2^-24.  The masses behind steps 3 and 5 are 64-bit fixed-point integers exp(z - max) * 2^40 summed with integer LDS atomics: the token is
+ * bit-reproducible for the same logits, parameters and u.  No sort of the vocabulary (radix selection over LDS histograms).
+ * Outputs: next_token[B]; probs_out[B][V] (row stride ld_probs; null = not wanted) = r; kept_out[B] (null = not wanted) = size of the kept set.  state (null = none;
+ * B == 1 only): the bookkeeping of afk_decode_select_greedy with this token - tokens_out[state[2] + tok_off] (tokens_out may be null), state[1 .. 3] += 1,
+ * x_out[H] = emb[token][:H].  temperature > 0, top_p > 0 (>= 1: off), top_k <= 0: off, V <= AFK_SAMPLE_MAX_V. */
+#define AFK_SAMPLE_MAX_V 8388608
+int afk_decode_sample(const float* logits, int64_t ld_logits, int B, int V, float temperature, int top_k, float top_p, const float* u, int64_t seed,
+                      const int* step_base, int step_off, int64_t* next_token, float* probs_out, int64_t ld_probs, int* kept_out, int64_t* tokens_out, int tok_off,
+                      int* state, const void* emb, int64_t ld_emb, int H, void* x_out, void* stream);
 /* The same launches for 2 .. 8 sequences decoded together (one new position each; the weights are still read once per step): M input rows h [M][K] (row stride
  * ldh) that are ALREADY normalised where the Linear follows a norm (Qwen2DecoderLayer :270 / :294, Qwen2Model.norm); pos[M] = position of each sequence's new token,
  * *start_dev = the cache slot all of them write; q_out [M][Hq*D] (row stride ldq); k_bs / vt_bs = batch strides of the K / V^T caches (elements).  Rounding points as above. */
