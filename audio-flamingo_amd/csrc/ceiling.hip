@@ -6,6 +6,8 @@
 // no global traffic inside the loop (mode 0) - and the same loop with the GEMM's LDS fragment reads added (mode 1: 24 ds_read_b128 per 32 MFMAs,
 // the 256x256x64 ping-pong kernel's ratio, gemm256.hip).  bench.py divides the GEMM's achieved rate by the mode-0 figure
 // (`roofline.frac_of_power_ceiling`); tools/measure_mfma_ceiling.py samples clock and socket power beside it -> profiles/r06_mfma_power_ceiling.md.
+// Modes 4 / 5 are modes 0 / 1 on v_mfma_f32_16x16x32_bf16: the same 8 waves per CU, 64 operand VGPRs, 64 accumulator VGPRs, 12 ds_read_b128 and FLOPs per
+// segment (32 MFMAs of 16 cycles for 16 of 32) - on N(0,1) operands the chip holds a different clock on the two shapes (profiles/gemm_mfma_shape_ab.md).
 #include "common.h"
 #include "../../include/afk.h"
 
@@ -13,7 +15,8 @@ namespace {
 
 constexpr int SEG = 16;   // MFMAs per segment: 2 x 2 output tiles x 4 k-steps (one MFMA segment of the ping-pong GEMM)
 
-template <int MODE>
+// MODE: 0 = registers only, 1 = + LDS fragment reads; MF = 32 | 16: MFMA shape
+template <int MODE, int MF>
 __global__ __launch_bounds__(512, 1) void mfma_ceiling_kernel(const bf16* __restrict__ src, float* __restrict__ sink, int iters) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -31,13 +34,20 @@ __global__ __launch_bounds__(512, 1) void mfma_ceiling_kernel(const bf16* __rest
         for (int i = tid; i < 4096; i += 512) ((bf16x8*)smem)[i] = s8[i];
         __syncthreads();
     }
-    f32x16 acc[2][2];
+    f32x16 acc[2][2];     // MF = 32: 2 x 2 blocks of 32 x 32
+    f32x4 acc16[4][4];    // MF = 16: 4 x 4 tiles of 16 x 16 (the same 64 VGPRs; the other array is dead)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc16[i][j][e] = 0.f;
     uint32_t lds = afk_lds_addr(smem) + lane * 16;
     for (int it = 0; it < iters; ++it) {
         if (MODE == 1) {
@@ -51,14 +61,31 @@ __global__ __launch_bounds__(512, 1) void mfma_ceiling_kernel(const bf16* __rest
             });
             afk_lds_wait0(a[0][0], a[0][1], a[0][2], a[0][3], a[1][0], a[1][1], a[1][2], a[1][3], b[0][0], b[1][1], b[0][2], b[1][3]);
         }
+        if constexpr (MF == 32) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+            for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][k], b[j][k], acc[i][j], 0, 0, 0);
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][k], b[j][k], acc[i][j], 0, 0, 0);
+        } else {
+            // operand [i][k] is fragment (16-row tile 2 i + (k >> 1), k-step k & 1): 4 x 4 tiles x 2 k-steps of 32 = the FLOPs of the 16 MFMAs above
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i >> 1][2 * (i & 1) + k], b[j >> 1][2 * (j & 1) + k], acc16[i][j], 0, 0, 0);
+        }
     }
     float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s += acc16[i][j][e];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -114,11 +141,11 @@ __global__ __launch_bounds__(256, 1) void mfma_pacing_kernel(const bf16* __restr
 }  // namespace
 
 extern "C" int afk_mfma_ceiling(int mode, int nblocks, int iters, const void* operands, float* sink, double* host_flops, void* stream) {
-    AFK_REQUIRE(mode >= 0 && mode <= 3, "afk_mfma_ceiling: mode %d (0 = register-resident operands, 1 = + LDS fragment reads, 2 / 3 = issue pacing of one wave per SIMD, "
-                "independent / dependent accumulators: sink[0] = cycles per MFMA)", mode);
+    AFK_REQUIRE(mode >= 0 && mode <= 5, "afk_mfma_ceiling: mode %d (0 = register-resident operands, 1 = + LDS fragment reads, 2 / 3 = issue pacing of one wave per SIMD, "
+                "independent / dependent accumulators: sink[0] = cycles per MFMA, 4 / 5 = modes 0 / 1 on v_mfma_f32_16x16x32_bf16)", mode);
     AFK_REQUIRE(nblocks > 0 && iters > 0 && operands && sink, "afk_mfma_ceiling: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (mode >= 2) {
+    if (mode == 2 || mode == 3) {
         if (mode == 2) mfma_pacing_kernel<false><<<nblocks, 256, 0, s>>>((const bf16*)operands, sink, iters);
         else mfma_pacing_kernel<true><<<nblocks, 256, 0, s>>>((const bf16*)operands, sink, iters);
         AFK_LAUNCH_CHECK("afk_mfma_ceiling");
@@ -126,14 +153,18 @@ extern "C" int afk_mfma_ceiling(int mode, int nblocks, int iters, const void* op
         return AFK_OK;
     }
     if (mode == 0) {
-        mfma_ceiling_kernel<0><<<nblocks, 512, 0, s>>>((const bf16*)operands, sink, iters);
+        mfma_ceiling_kernel<0, 32><<<nblocks, 512, 0, s>>>((const bf16*)operands, sink, iters);
+    } else if (mode == 4) {
+        mfma_ceiling_kernel<0, 16><<<nblocks, 512, 0, s>>>((const bf16*)operands, sink, iters);
     } else {
         static bool attr = false;
         if (!attr) {
-            hipFuncSetAttribute((const void*)mfma_ceiling_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 16384);
+            hipFuncSetAttribute((const void*)mfma_ceiling_kernel<1, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 16384);
+            hipFuncSetAttribute((const void*)mfma_ceiling_kernel<1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 16384);
             attr = true;
         }
-        mfma_ceiling_kernel<1><<<nblocks, 512, 65536 + 16384, s>>>((const bf16*)operands, sink, iters);
+        if (mode == 1) mfma_ceiling_kernel<1, 32><<<nblocks, 512, 65536 + 16384, s>>>((const bf16*)operands, sink, iters);
+        else mfma_ceiling_kernel<1, 16><<<nblocks, 512, 65536 + 16384, s>>>((const bf16*)operands, sink, iters);
     }
     AFK_LAUNCH_CHECK("afk_mfma_ceiling");
     if (host_flops) *host_flops = (double)nblocks * 8.0 * iters * SEG * 2.0 * 32 * 32 * 16;

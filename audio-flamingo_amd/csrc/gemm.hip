@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_k128(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) gemm_store_block32_body<-1>(p, m0 + wm * 64 + i * 32 + l31, n0 + wn * 64 + j * 32, hi, acc[i][j]);
+        for (int j = 0; j < 2; ++j) gemm_store_block32_body<-1, 32>(p, m0 + wm * 64 + i * 32, n0 + wn * 64 + j * 32, lane, acc[i][j]);
 }
 
 // measured on the AF3-7B decode step (ms/token): M = 1 3.85 (MFMA split-K tiles: 6.5); M = 2 6.3, M = 4 6.4, M = 8 7.6 against 5.3-5.7 on
@@ -227,6 +227,24 @@ int g_variant = 0;  // 0 auto, 1 force 128x128, 2 force 256x256 (8-wave ping-pon
                     // (gemm256f8.hip); env AFK_GEMM256 = pp | w4 | f8
 int g_gm = 0;       // rasterization group height override (0 = default 8)
 int g_wide = 1;     // 16-byte epilogue form allowed (afk_gemm_set_variant bit 4 clears it: A/B experiments)
+int g_mfma = 0;     // MFMA shape of the 256x256 kernels: 0 = the dispatch rule (gemm_mfma_of), 1 = 32x32x16, 2 = 16x16x32 (afk_gemm_set_mfma / env AFK_GEMM_MFMA)
+
+// Shapes each 256x256 kernel form carries (bit 0 = 32x32x16, bit 1 = 16x16x32); form 0 = NT, 1 = NN, 2 = TN
+constexpr int mfma_shapes(int form) { return form == 0 ? AFK_MFMA_SHAPES_NT : form == 1 ? AFK_MFMA_SHAPES_NN : AFK_MFMA_SHAPES_TN; }
+// THE dispatch rule (next to the tile / split-K plans of gemm_impl): which MFMA shape a 256x256 launch runs, per kernel form, from the per-shape table of
+// profiles/gemm_mfma_shape_ab.md.  A tie keeps 32x32x16.
+// Measured (table (c) there): NT 16x16x32 on every shape of the step, encoder (K = 1280) and decoder (K >= 3584) alike, so no shape boundary; NN and TN 32x32x16.
+constexpr int AFK_MFMA_RULE_NT = 16, AFK_MFMA_RULE_NN = 32, AFK_MFMA_RULE_TN = 32;
+int gemm_mfma_of(int form) {
+    static const int env = [] {   // read once, at the first 256x256 launch: whole-step A/Bs run on one build
+        const char* e = getenv("AFK_GEMM_MFMA");
+        return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 0;
+    }();
+    const int sel = g_mfma ? g_mfma : env;
+    if (sel == 1) return 32;
+    if (sel == 2) return 16;
+    return form == 0 ? AFK_MFMA_RULE_NT : form == 1 ? AFK_MFMA_RULE_NN : AFK_MFMA_RULE_TN;
+}
 
 hipEvent_t prof_next_event() {
     if (g_prof.used == g_prof.pool.size()) {
@@ -255,6 +273,19 @@ extern "C" int afk_gemm_set_variant(int v) {
     g_variant = base;
     return AFK_OK;
 }
+
+extern "C" int afk_gemm_set_mfma(int v) {
+    // 0 = the dispatch rule, 1 = v_mfma_f32_32x32x16_bf16, 2 = v_mfma_f32_16x16x32_bf16 in the 256x256 kernels (NT, NN, TN); a shape that no kernel of this
+    // build carries is refused (the losing shape of a kernel is built under make PROBES=1 only, as the rejected schedules are)
+    AFK_REQUIRE(v >= 0 && v <= 2, "afk_gemm_set_mfma: %d (0 = dispatch rule, 1 = 32x32x16, 2 = 16x16x32)", v);
+    constexpr int any = AFK_MFMA_SHAPES_NT | AFK_MFMA_SHAPES_NN | AFK_MFMA_SHAPES_TN;
+    AFK_REQUIRE(v == 0 || (any >> (v - 1)) & 1, "afk_gemm_set_mfma: no 256x256 kernel of this libafk.so carries the %s shape; build with make PROBES=1",
+                v == 1 ? "32x32x16" : "16x16x32");
+    g_mfma = v;
+    return AFK_OK;
+}
+// bit 0 = 32x32x16, bit 1 = 16x16x32: the shapes form (0 NT, 1 NN, 2 TN) was built with
+extern "C" int afk_gemm_mfma_shapes(int form) { return form >= 0 && form <= 2 ? mfma_shapes(form) : 0; }
 
 extern "C" int afk_prof_enable(int on) {
     std::lock_guard<std::mutex> lk(g_prof.mu);
@@ -411,7 +442,7 @@ static int gemm_impl(int trans_a, int trans_b, const void* A, int64_t lda, const
         if (g > 2048) g = 2048;
         hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(g), dim3(256), 0, st, p);
     } else if (trans_b) {
-        if (int e = afk_launch_gemm256t(p, trans_a, st)) return e;
+        if (int e = afk_launch_gemm256t(p, trans_a, gemm_mfma_of(trans_a ? 2 : 1), st)) return e;
         if (splits > 1) {
             int g = (int)afk_cdiv((int64_t)M * (N / 4), 256);
             if (g > 2048) g = 2048;
@@ -419,9 +450,9 @@ static int gemm_impl(int trans_a, int trans_b, const void* A, int64_t lda, const
         }
     } else if (use256) {
 #ifdef AFK_PROBES
-        if (int e = persist_q ? afk_launch_gemm256q(p, st) : persist ? afk_launch_gemm256p(p, st) : f8 ? afk_launch_gemm256f8(p, impl256 - 10, st) : w4 ? afk_launch_gemm256w4(p, impl256 - 3, st) : afk_launch_gemm256(p, st)) return e;
+        if (int e = persist_q ? afk_launch_gemm256q(p, st) : persist ? afk_launch_gemm256p(p, st) : f8 ? afk_launch_gemm256f8(p, impl256 - 10, st) : w4 ? afk_launch_gemm256w4(p, impl256 - 3, st) : afk_launch_gemm256(p, gemm_mfma_of(0), st)) return e;
 #else
-        if (int e = afk_launch_gemm256(p, st)) return e;
+        if (int e = afk_launch_gemm256(p, gemm_mfma_of(0), st)) return e;
 #endif
     } else {
         hipLaunchKernelGGL(gemm_nt_bf16_k128, dim3((unsigned)nwg, (unsigned)splits), dim3(256), NSTAGE * STAGE_BYTES, st, p);

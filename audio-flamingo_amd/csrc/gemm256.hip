@@ -46,7 +46,9 @@ constexpr int LDS_BYTES = 2 * BUF_BYTES;  // 128 KiB
     } while (0)
 
 // EPI: compile-time epilogue flags (gemm_common.h), -1 = runtime flags / narrow stores / split-K partials
-template <int EPI>
+// MF: MFMA shape (gemm_common.h): 32 = 16 x v_mfma_f32_32x32x16_bf16 per MFMA segment, 16 = 32 x v_mfma_f32_16x16x32_bf16 (same cycles, same
+// fragments per segment, same 64 + 128 VGPRs); on N(0,1) operands the chip holds a higher clock on the second (profiles/gemm_mfma_shape_ab.md)
+template <int EPI, int MF>
 __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -113,20 +115,15 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
     };
 
     // ---- fragment offsets (bytes within an operand image); the swizzle term is lane-constant
-    const int swz_l = (lane >> 1) & 7;
+    // fragment x = 0..3 of a 32-row tile (gemm_common.h: MF = 32: k-step x; MF = 16: 16-row half x >> 1, k-step x & 1)
     int koffb[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) koffb[s] = ((2 * s + hi) ^ swz_l) << 4;
-    const int a_row0 = (wm * 128 + l31) * ROWB;            // + i*32*ROWB, i = 0..3 (i<2: MEM_a, i>=2: MEM_b)
-    const int b_row0 = OP_BYTES + (wn * 64 + l31) * ROWB;  // + j*32*ROWB, j = 0..1
+    for (int x = 0; x < 4; ++x) koffb[x] = gemm_frag_rowoff<MF>(x) * ROWB + gemm_frag_koff<MF>(x, lane);
+    const int a_row0 = (wm * 128 + gemm_frag_row<MF>(lane)) * ROWB;            // + i*32*ROWB, i = 0..3 (i<2: MEM_a, i>=2: MEM_b)
+    const int b_row0 = OP_BYTES + (wn * 64 + gemm_frag_row<MF>(lane)) * ROWB;  // + j*32*ROWB, j = 0..1
 
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    GemmAcc<MF> acc;
+    acc.zero();
 
     const int T = p.K / BK;
     // ---- prologue: X0 Y0 X1, then make X0 visible to everyone
@@ -142,12 +139,39 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
     if (wm == 1) AFK_BARRIER();  // group 1 runs one segment behind group 0
 
     bf16x8 bf[2][4], af[2][4];
-    // one LDS-DMA piece slotted behind every group of MFMAs (issue cost hides in the MFMA shadow)
-#define AFK_MFMA4(ACC0, s)                                                                                         \
-    do {                                                                                                           \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)          \
-            acc[ACC0 + i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[j_][s], af[i_][s], acc[ACC0 + i_][j_], 0, 0, 0); \
-    } while (0)
+    // one LDS-DMA piece slotted behind every group of MFMAs (issue cost hides in the MFMA shadow).  A group = 128 matrix-pipe cycles:
+    //   MF = 32: k-step g, 2 x 2 blocks (4 MFMAs of 32 cycles);  MF = 16: k-step g >> 1, A block g & 1, its 2 x 4 tiles (8 MFMAs of 16 cycles)
+    auto mfma_group = [&](auto acc0_, auto g_) {
+        constexpr int ACC0 = decltype(acc0_)::value, g = decltype(g_)::value;
+        if constexpr (MF == 32) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc.mma(ACC0 + i, j, bf[j][g], af[i][g]);
+        } else {
+            constexpr int s = g >> 1, i = g & 1;
+#pragma unroll
+            for (int ih = 0; ih < 2; ++ih)
+#pragma unroll
+                for (int jt = 0; jt < 4; ++jt) acc.mma(2 * (ACC0 + i) + ih, jt, bf[jt >> 1][2 * (jt & 1) + s], af[i][2 * ih + s]);
+        }
+    };
+    // half a group (64 cycles) of MFMA_b: slot q = 0..7.  MF = 32: k-step q >> 1, A block q & 1 (2 MFMAs); MF = 16: k-step q >> 2, A block (q >> 1) & 1,
+    // its 16-row half q & 1 (4 MFMAs)
+    auto mfma_slot = [&](auto acc0_, auto q_) {
+        constexpr int ACC0 = decltype(acc0_)::value, q = decltype(q_)::value;
+        if constexpr (MF == 32) {
+            constexpr int s = q >> 1, i = q & 1;
+            acc.mma(ACC0 + i, 0, bf[0][s], af[i][s]);
+            acc.mma(ACC0 + i, 1, bf[1][s], af[i][s]);
+        } else {
+            constexpr int s = q >> 2, i = (q >> 1) & 1, ih = q & 1;
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) acc.mma(2 * (ACC0 + i) + ih, jt, bf[jt >> 1][2 * (jt & 1) + s], af[i][2 * ih + s]);
+        }
+    };
+    using afk_c2 = std::integral_constant<int, 2>;
+#define AFK_MFMA4(ACC0, g) mfma_group(std::integral_constant<int, ACC0>{}, std::integral_constant<int, g>{})
     // Branch-free steady state: past the last K-tile the prefetch index is clamped to T-1, i.e. the tail re-loads the
     // last tile into slots nobody reads again (dead by the same lifetime argument), so the vmcnt ladder never changes.
     for (int t = 0; t < T; ++t) {
@@ -194,20 +218,15 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
         AFK_BARRIER();
         // ================= MFMA_b(t) (+ X(t+2): 6 pieces)
         __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                acc[2 + i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[0][s], af[i][s], acc[2 + i][0], 0, 0, 0);
-                acc[2 + i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[1][s], af[i][s], acc[2 + i][1], 0, 0, 0);
-                const int piece = 2 * s + i;  // 0..7, pieces 0..5 carry a DMA
-                if (piece < 6) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_global_load_lds((gbl_void*)(xsrc[piece] + ox), (lds_void*)(bx + xdst[piece]), 16, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+        afk_static_for<8>([&](auto q_) {
+            constexpr int piece = decltype(q_)::value;  // 0..7, pieces 0..5 carry a DMA
+            mfma_slot(afk_c2{}, q_);
+            if constexpr (piece < 6) {
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_global_load_lds((gbl_void*)(xsrc[piece] + ox), (lds_void*)(bx + xdst[piece]), 16, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
             }
-        }
+        });
         __builtin_amdgcn_s_setprio(0);
         AFK_VMCNT(8);
         AFK_BARRIER();
@@ -220,6 +239,8 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
         // waves wn = 0, 1 hold gate columns, wn = 2, 3 the up columns of the SAME 64 features and rows: the up waves park their
         // bf16 pieces in the (now idle) operand buffers, the gate waves pick them up and write h = bf16(bf16(silu(g)) * u) beside g
         // (same arithmetic as silu_mul_fwd_kernel on the bf16-rounded GEMM results: bit-identical to the two-kernel form).
+        // (l31 and hi below are the row and the 16-byte column chunk of a lane AFTER the lane-pair exchange - the same in both MFMA shapes, gemm_common.h -
+        // so both waves of a pair use one piece -> (row, column) map and the exchange keeps its shape)
         typedef __attribute__((ext_vector_type(8))) __bf16 b8;
         const int I = p.N >> 1;
         const bool up = wn >= 2;
@@ -232,12 +253,15 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
+                    // piece q = (i, j, t): row 32 i + (lane & 31), columns 32 j + 16 t + 8 (lane >> 5) + 0..7 in both MFMA shapes (gemm_lane_swap)
+                    const f32x16 blk = acc.block(i, j);
                     b8 o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[i][j][8 * t + e]), __float_as_uint(acc[i][j][8 * t + 4 + e]), false, false);
-                        o[e] = (bf16)(__uint_as_float(r[0]) * p.alpha);
-                        o[4 + e] = (bf16)(__uint_as_float(r[1]) * p.alpha);
+                        float v0, v1;
+                        gemm_lane_swap<MF>(blk[8 * t + e], blk[8 * t + 4 + e], v0, v1);
+                        o[e] = (bf16)(v0 * p.alpha);
+                        o[4 + e] = (bf16)(v1 * p.alpha);
                     }
                     pc[(i * 2 + j) * 2 + t] = o;
                 }
@@ -290,11 +314,14 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
                     const int n = n0 + wn * 64 + j * 32 + 16 * t + 8 * hi;
                     b8 bv;
                     if constexpr ((EPI & AFK_GEMM_BIAS) != 0) bv = *(const b8*)(p.bias + n);
+                    const f32x16 blk = acc.block(i, j);
                     b8 o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[i][j][8 * t + e]), __float_as_uint(acc[i][j][8 * t + 4 + e]), false, false);
-                        float v0 = __uint_as_float(r[0]) * p.alpha, v1 = __uint_as_float(r[1]) * p.alpha;
+                        float v0, v1;
+                        gemm_lane_swap<MF>(blk[8 * t + e], blk[8 * t + 4 + e], v0, v1);
+                        v0 *= p.alpha;
+                        v1 *= p.alpha;
                         if constexpr ((EPI & AFK_GEMM_BIAS) != 0) {
                             v0 += (float)bv[e];
                             v1 += (float)bv[4 + e];
@@ -339,12 +366,12 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
         }
         return;
     }
-    // ---- epilogue: lane holds row m = ..+l31 and n = ..+8q+4hi+{0..3}
+    // ---- epilogue: 32 x 32 blocks (gemm_common.h)
     if (AFK_GM_NOEPI(p)) return;  // -DAFK_PROBES builds only: timing probe (afk_gemm_set_variant(2 + 256 * 0x40), wrong results): the kernel without its epilogue
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) gemm_store_block32<EPI>(p, m0 + wm * 128 + i * 32 + l31, n0 + wn * 64 + j * 32, hi, acc[i][j]);
+        for (int j = 0; j < 2; ++j) gemm_store_block32<EPI, MF>(p, m0 + wm * 128 + i * 32, n0 + wn * 64 + j * 32, lane, acc.block(i, j));
 }
 
 }  // namespace
@@ -353,11 +380,12 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
 #define AFK_EPI_LIST(X) X(0) X(AFK_GEMM_BIAS) X(AFK_GEMM_RESIDUAL) X(AFK_GEMM_BIAS | AFK_GEMM_RESIDUAL) X(AFK_GEMM_BIAS | AFK_GEMM_GELU) \
     X(AFK_GEMM_BIAS | AFK_GEMM_GELU | AFK_GEMM_RESIDUAL) X(AFK_GEMM_ACCUM) X(AFK_GEMM_SWIGLU_FWD) X(AFK_GEMM_SWIGLU_BWD) X(AFK_GEMM_ROPE) X(AFK_GEMM_ROPE | AFK_GEMM_BIAS) X(-1)
 
-int afk_launch_gemm256(const GemmArgs& p, hipStream_t st) {
+template <int MF>
+static int launch_gemm256(const GemmArgs& p, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
-#define AFK_SET(F)                                                                                                                       \
-    if (hipFuncSetAttribute((const void*)gemm_nt_bf16_k256<(F)>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) \
+#define AFK_SET(F)                                                                                                                           \
+    if (hipFuncSetAttribute((const void*)gemm_nt_bf16_k256<(F), MF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) \
         return afk_set_error(AFK_ERR_LAUNCH, "gemm256: cannot reserve %d bytes of LDS", LDS_BYTES);
         AFK_EPI_LIST(AFK_SET)
 #undef AFK_SET
@@ -366,16 +394,24 @@ int afk_launch_gemm256(const GemmArgs& p, hipStream_t st) {
     const int64_t nwg = (int64_t)p.ntm * p.ntn;
     const int f = (p.wide && p.splits <= 1) ? p.flags : -1;
     switch (f) {
-#define AFK_CASE(F)                                                                                          \
-    case (F):                                                                                                \
-        if ((F) == -1) afk_count(AFK_CNT_GEMM_GENERIC);                                                      \
-        hipLaunchKernelGGL(gemm_nt_bf16_k256<(F)>, dim3((unsigned)nwg), dim3(512), LDS_BYTES, st, p);        \
+#define AFK_CASE(F)                                                                                              \
+    case (F):                                                                                                    \
+        if ((F) == -1) afk_count(AFK_CNT_GEMM_GENERIC);                                                          \
+        hipLaunchKernelGGL((gemm_nt_bf16_k256<(F), MF>), dim3((unsigned)nwg), dim3(512), LDS_BYTES, st, p);      \
         break;
         AFK_EPI_LIST(AFK_CASE)
 #undef AFK_CASE
         default:   // an epilogue outside the list: runtime-flag instantiation
             afk_count(AFK_CNT_GEMM_GENERIC);
-            hipLaunchKernelGGL(gemm_nt_bf16_k256<-1>, dim3((unsigned)nwg), dim3(512), LDS_BYTES, st, p);
+            hipLaunchKernelGGL((gemm_nt_bf16_k256<-1, MF>), dim3((unsigned)nwg), dim3(512), LDS_BYTES, st, p);
     }
     return AFK_OK;
+}
+
+int afk_launch_gemm256(const GemmArgs& p, int mf, hipStream_t st) {
+    if constexpr ((AFK_MFMA_SHAPES_NT & 2) != 0)
+        if (mf == 16) return launch_gemm256<16>(p, st);
+    if constexpr ((AFK_MFMA_SHAPES_NT & 1) != 0)
+        if (mf == 32) return launch_gemm256<32>(p, st);
+    return afk_set_error(AFK_ERR_UNSUPPORTED, "gemm256: the %s MFMA shape of the NT kernel is built under make PROBES=1 only", mf == 16 ? "16x16x32" : "32x32x16");
 }

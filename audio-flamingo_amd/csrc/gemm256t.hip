@@ -44,7 +44,6 @@ typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
         __builtin_amdgcn_global_load_lds((gbl_void*)(SRCPTR), (lds_void*)(DSTPTR), 16, 0, 0);             \
         __builtin_amdgcn_sched_barrier(0);                                                                \
     } while (0)
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 
 __device__ __forceinline__ int tswz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 
@@ -52,17 +51,24 @@ __device__ __forceinline__ int tswz(int r) { return ((r & 3) << 2) | ((r >> 2) &
 // The swizzle term of a tr-read address does not depend on the k-step s (16*s leaves r&3 and (r>>2)&3 unchanged), so the
 // two byte offsets of a (tile, piece) pair are lane constants: they are computed once per kernel and every read is
 // "base + immediate" (s*8192 fits the 16-bit ds offset field) - no VALU in the MEM segments.
-__device__ __forceinline__ int tr_off(int tile32, int pc, int lane) {
-    const int g = lane >> 4, i = lane & 15, hi = g >> 1;
-    const int chunk = 4 * tile32 + 2 * (g & 1) + ((i & 3) >> 1);
-    const int r = 8 * hi + (i >> 2) + 4 * pc;  // + 16*s
+//
+// 16x16x32 shape (MF = 16): lane -> column 16*tile16 + (lane&15), k = 32*s + 8*(lane>>4) + 0..7: the 16-lane group g reads k-rows 8g + 4pc + 0..3 of
+// the 16 columns of its tile; the two 32-lane halves of a read touch k-rows {0..3, 8..11} and {16..19, 24..27} (+ 4 for pc = 1), whose swizzle terms
+// tswz differ in bit 1 between the two groups of a half and in bits 2, 3 between the rows of a group: conflict-free (tests/test_gemm_frag_map_cpu.py).
+// 32*s leaves the swizzle term unchanged as well, so the offsets stay lane constants + immediates (s*16384).
+// Fragment x of a 32-column tile: MF = 32: k-step x (0..3); MF = 16: 16-column half x >> 1, k-step x & 1 - as for the k-contiguous image.
+template <int MF>
+__device__ __forceinline__ int tr_off(int tile, int pc, int lane) {   // tile: 32-column tile (MF = 32) or 16-column tile (MF = 16)
+    const int g = lane >> 4, i = lane & 15;
+    const int chunk = MF == 16 ? 2 * tile + ((i & 3) >> 1) : 4 * tile + 2 * (g & 1) + ((i & 3) >> 1);
+    const int r = (MF == 16 ? 8 * g : 8 * (g >> 1)) + (i >> 2) + 4 * pc;  // + 16*s (MF = 32), + 32*s (MF = 16)
     return r * TROW + ((chunk ^ tswz(r)) << 4) + 8 * (i & 1);
 }
 // opaque-asm reads (common.h: the builtin form drags an s_waitcnt vmcnt(0) into the loop); every MEM segment ends with
 // AFK_LGKMCNT0 + a scheduling barrier before the first MFMA, which is the wait these reads need
-template <int S>
+template <int MF, int S>
 __device__ __forceinline__ bf16x8 tr_frag(uint32_t buf, int off0, int off1) {
-    return afk_lds_tr_frag<S * 16 * TROW>(buf + off0, buf + off1);
+    return afk_lds_tr_frag<S * (48 - MF) * TROW>(buf + off0, buf + off1);   // k-step S starts at k-row 16 S (MF = 32) / 32 S (MF = 16): S * (48 - MF) rows
 }
 
 // per-lane source of one LDS-DMA piece (1 KiB = 2 k-rows x 512 B) of a transposed image
@@ -82,7 +88,8 @@ __device__ __forceinline__ TSrc tsrc(const bf16* mat, int unit, int col0, int nc
 }
 
 // EPI: compile-time epilogue flags (gemm_common.h: one small epilogue instead of every variant inlined at each store site), -1 = runtime
-template <bool AT, int EPI>
+// MF: MFMA shape, 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16 (gemm_common.h; only fragments, MFMA calls and accumulator indexing differ)
+template <bool AT, int EPI, int MF>
 __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -154,13 +161,8 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
     const bf16* tbase[NX + NY];
 #pragma unroll
     for (int j = 0; j < NX + NY; ++j) tbase[j] = (AT || j < 4) ? tr_src[j].base + (int64_t)tr_src[j].krow * tr_ld[j] : nullptr;
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    GemmAcc<MF> acc;
+    acc.zero();
 
     const bool ragged = (KL % BK) != 0;
   // the whole pipeline twice: RAG = false (K a multiple of 64: every training shape) never clamps, RAG = true is the general form
@@ -180,22 +182,34 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
     };
     auto issue = [&](int j, int t_src, int parity) { AFK_DMA_PTR(src_of(j, t_src), smem + parity * BUF_BYTES + dst[j]); };
 
-    // lane-constant tr-read offsets: B tiles wn*2+j, A tiles wm*4+i (TN)
-    int tob[2][2], toa[4][2];
+    // lane-constant tr-read offsets: B tiles wn*2+j, A tiles wm*4+i (TN); MF = 16: [tile][h][pc] = 16-column half h of the 32-column tile
+    constexpr int NH = MF == 16 ? 2 : 1;
+    int tob[2][NH][2], toa[4][NH][2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int pc = 0; pc < 2; ++pc) tob[j][pc] = OP_BYTES + tr_off(wn * 2 + j, pc, lane);
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int pc = 0; pc < 2; ++pc) tob[j][h][pc] = OP_BYTES + tr_off<MF>((wn * 2 + j) * NH + h, pc, lane);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int pc = 0; pc < 2; ++pc) toa[i][pc] = AT ? tr_off(wm * 4 + i, pc, lane) : 0;
-    // fragment offsets for the k-contiguous A image (NN)
-    const int swz_l = (lane >> 1) & 7;
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int pc = 0; pc < 2; ++pc) toa[i][h][pc] = AT ? tr_off<MF>((wm * 4 + i) * NH + h, pc, lane) : 0;
+    // fragment x = 0..3 of a 32-column tile, k-steps [KS0, KS0 + NKS) of the tile: MF = 32 -> k-step x; MF = 16 -> half x >> 1, k-step x & 1
+    // (TN reads half a tile per phase: x = 0, 1 with KS0 = the phase's first k-step - MF = 32: k-step KS0 + x; MF = 16: half x, k-step KS0)
+    auto tr_read = [&](uint32_t lbuf, const int (&to)[NH][2], auto x_, auto ks0_) {
+        constexpr int x = decltype(x_)::value, ks0 = decltype(ks0_)::value;
+        if constexpr (MF == 32) return tr_frag<MF, ks0 + x>(lbuf, to[0][0], to[0][1]);
+        else if constexpr (AT) return tr_frag<MF, ks0>(lbuf, to[x][0], to[x][1]);
+        else return tr_frag<MF, (x & 1)>(lbuf, to[x >> 1][0], to[x >> 1][1]);
+    };
+    // fragment offsets for the k-contiguous A image (NN), as in gemm256.hip
     int koffb[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) koffb[s] = ((2 * s + hi) ^ swz_l) << 4;
-    const int a_row0 = (wm * 128 + l31) * 128;
+    for (int x = 0; x < 4; ++x) koffb[x] = gemm_frag_rowoff<MF>(x) * 128 + gemm_frag_koff<MF>(x, lane);
+    const int a_row0 = (wm * 128 + gemm_frag_row<MF>(lane)) * 128;
 
     // ------------------------------------------------------------------ prologue: X0 Y0 X1
 #pragma unroll
@@ -218,11 +232,11 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
         const uint32_t lbuf = lds0 + (t & 1) * BUF_BYTES;
         const int t1 = min(t + 1, T - 1), t2 = min(t + 2, T - 1);
         const int e1 = (t + 1) & 1, e2 = t & 1;
-        if (!AT) {
+        if constexpr (!AT) {
             // ================= NN  MEM_a: Bt fragments (whole tile) + A rows 0..63
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-                afk_static_for<4>([&](auto s_) { constexpr int s = decltype(s_)::value; bf[j][s] = tr_frag<s>(lbuf, tob[j][0], tob[j][1]); });
+                afk_static_for<4>([&](auto x_) { bf[j][decltype(x_)::value] = tr_read(lbuf, tob[j], x_, std::integral_constant<int, 0>{}); });
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -232,14 +246,22 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
             AFK_BARRIER();
             // ================= MFMA_a (+ Y(t+1))
             __builtin_amdgcn_s_setprio(1);
+            afk_static_for<4>([&](auto g_) {   // groups of 128 matrix-pipe cycles, as in gemm256.hip
+                constexpr int g = decltype(g_)::value;
+                if constexpr (MF == 32) {
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
+                    for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int i = 0; i < 2; ++i)
+                        for (int j = 0; j < 2; ++j) acc.mma(i, j, bf[j][g], af[i][g]);
+                } else {
+                    constexpr int s = g >> 1, i = g & 1;
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = MFMA(bf[j][s], af[i][s], acc[i][j]);
-                if (s < 2) issue(NX + s, t1, e1);
-            }
+                    for (int ih = 0; ih < 2; ++ih)
+#pragma unroll
+                        for (int jt = 0; jt < 4; ++jt) acc.mma(2 * i + ih, jt, bf[jt >> 1][2 * (jt & 1) + s], af[i][2 * ih + s]);
+                }
+                if constexpr (g < 2) issue(NX + g, t1, e1);
+            });
             __builtin_amdgcn_s_setprio(0);
             AFK_VMCNT(8);
             AFK_BARRIER();
@@ -253,16 +275,19 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
             AFK_BARRIER();
             // ================= MFMA_b (+ X(t+2))
             __builtin_amdgcn_s_setprio(1);
+            afk_static_for<8>([&](auto q_) {   // slots of 64 matrix-pipe cycles
+                constexpr int piece = decltype(q_)::value;
+                if constexpr (MF == 32) {
+                    constexpr int s = piece >> 1, i = piece & 1;
+                    acc.mma(2 + i, 0, bf[0][s], af[i][s]);
+                    acc.mma(2 + i, 1, bf[1][s], af[i][s]);
+                } else {
+                    constexpr int s = piece >> 2, i = (piece >> 1) & 1, ih = piece & 1;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    acc[2 + i][0] = MFMA(bf[0][s], af[i][s], acc[2 + i][0]);
-                    acc[2 + i][1] = MFMA(bf[1][s], af[i][s], acc[2 + i][1]);
-                    const int piece = 2 * s + i;
-                    if (piece < 6) issue(piece, t2, e2);
+                    for (int jt = 0; jt < 4; ++jt) acc.mma(2 * (2 + i) + ih, jt, bf[jt >> 1][2 * (jt & 1) + s], af[i][2 * ih + s]);
                 }
-            }
+                if constexpr (piece < 6) issue(piece, t2, e2);
+            });
             __builtin_amdgcn_s_setprio(0);
             AFK_VMCNT(8);
             AFK_BARRIER();
@@ -271,27 +296,29 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
 #pragma unroll
             for (int ph = 0; ph < 2; ++ph) {
                 // ================= TN  MEM: fragments of k-steps {2ph, 2ph+1} of both images
-                afk_static_for<2>([&](auto s_) {
-                    constexpr int s = decltype(s_)::value;
+                // (first k-step of phase ph: 2 ph of four 16-wide, ph of two 32-wide)
+                afk_static_for<2>([&](auto x_) {
+                    constexpr int x = decltype(x_)::value;
+                    constexpr int KS = MF == 16 ? 1 : 2;
                     if (ph == 0) {
 #pragma unroll
-                        for (int j = 0; j < 2; ++j) bf[j][s] = tr_frag<s>(lbuf, tob[j][0], tob[j][1]);
+                        for (int j = 0; j < 2; ++j) bf[j][x] = tr_read(lbuf, tob[j], x_, std::integral_constant<int, 0>{});
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) af[i][s] = tr_frag<s>(lbuf, toa[i][0], toa[i][1]);
+                        for (int i = 0; i < 4; ++i) af[i][x] = tr_read(lbuf, toa[i], x_, std::integral_constant<int, 0>{});
                     } else {
 #pragma unroll
-                        for (int j = 0; j < 2; ++j) bf[j][s] = tr_frag<2 + s>(lbuf, tob[j][0], tob[j][1]);
+                        for (int j = 0; j < 2; ++j) bf[j][x] = tr_read(lbuf, tob[j], x_, std::integral_constant<int, KS>{});
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) af[i][s] = tr_frag<2 + s>(lbuf, toa[i][0], toa[i][1]);
+                        for (int i = 0; i < 4; ++i) af[i][x] = tr_read(lbuf, toa[i], x_, std::integral_constant<int, KS>{});
                     }
                 });
                 AFK_LGKMCNT0();
                 if (RAG && kvalid < BK) {  // block-uniform, ragged last tile only (the RAG = false pipeline has no such tile): zero the A contribution of k >= K
 #pragma unroll
-                    for (int s = 0; s < 2; ++s)
+                    for (int s = 0; s < 2; ++s)   // fragment s of the phase: MF = 32: k-step 2 ph + s; MF = 16: column half s of k-step ph
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
-                            const bool dead = 16 * (2 * ph + s) + 8 * hi + e >= kvalid;
+                            const bool dead = (MF == 16 ? 32 * ph + 8 * (lane >> 4) : 16 * (2 * ph + s) + 8 * hi) + e >= kvalid;
 #pragma unroll
                             for (int i = 0; i < 4; ++i)
                                 if (dead) af[i][s][e] = (bf16)0.f;
@@ -301,19 +328,22 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
                 AFK_BARRIER();
                 // ================= MFMA (+ Y(t+1) in phase 0, X(t+2) in phase 1: 4 pieces each)
                 __builtin_amdgcn_s_setprio(1);
+                afk_static_for<8>([&](auto q_) {   // slots of 64 matrix-pipe cycles
+                    constexpr int piece = decltype(q_)::value;  // 0..7, even pieces carry a DMA
+                    if constexpr (MF == 32) {
+                        constexpr int s = piece >> 2, i = piece & 3;
+                        acc.mma(i, 0, bf[0][s], af[i][s]);
+                        acc.mma(i, 1, bf[1][s], af[i][s]);
+                    } else {
+                        constexpr int i = piece >> 1, ih = piece & 1;   // A block i, its 16-column half ih, against the 4 B tiles
 #pragma unroll
-                for (int s = 0; s < 2; ++s) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        acc[i][0] = MFMA(bf[0][s], af[i][s], acc[i][0]);
-                        acc[i][1] = MFMA(bf[1][s], af[i][s], acc[i][1]);
-                        const int piece = 4 * s + i;  // 0..7, even pieces carry a DMA
-                        if ((piece & 1) == 0) {
-                            if (ph == 0) issue(NX + (piece >> 1), t1, e1);
-                            else issue(piece >> 1, t2, e2);
-                        }
+                        for (int jt = 0; jt < 4; ++jt) acc.mma(2 * i + ih, jt, bf[jt >> 1][jt & 1], af[i][ih]);
                     }
-                }
+                    if constexpr ((piece & 1) == 0) {
+                        if (ph == 0) issue(NX + (piece >> 1), t1, e1);
+                        else issue(piece >> 1, t2, e2);
+                    }
+                });
                 __builtin_amdgcn_s_setprio(0);
                 AFK_VMCNT(8);
                 AFK_BARRIER();
@@ -329,7 +359,7 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) gemm_store_block32<EPI>(p, m0 + wm * 128 + i * 32 + l31, n0 + wn * 64 + j * 32, hi, acc[i][j]);
+        for (int j = 0; j < 2; ++j) gemm_store_block32<EPI, MF>(p, m0 + wm * 128 + i * 32, n0 + wn * 64 + j * 32, lane, acc.block(i, j));
 }
 
 }  // namespace
@@ -337,12 +367,12 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
 // weight gradients write or accumulate plain bf16 (flags 0 / ACCUM); the generic instantiation serves split-K partials and the rest
 #define AFK_EPI_LIST(X) X(0) X(AFK_GEMM_ACCUM) X(-2) X(-1)
 
-int afk_launch_gemm256t(const GemmArgs& p, int trans_a, hipStream_t st) {
+template <bool AT, int MF>
+static int launch_gemm256t(const GemmArgs& p, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
-#define AFK_SET(F)                                                                                                                                \
-    if (hipFuncSetAttribute((const void*)gemm_xt_bf16_k256<false, (F)>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess || \
-        hipFuncSetAttribute((const void*)gemm_xt_bf16_k256<true, (F)>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess)    \
+#define AFK_SET(F)                                                                                                                              \
+    if (hipFuncSetAttribute((const void*)gemm_xt_bf16_k256<AT, (F), MF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) \
         return afk_set_error(AFK_ERR_LAUNCH, "gemm256t: cannot reserve %d bytes of LDS", LDS_BYTES);
         AFK_EPI_LIST(AFK_SET)
 #undef AFK_SET
@@ -353,18 +383,32 @@ int afk_launch_gemm256t(const GemmArgs& p, int trans_a, hipStream_t st) {
     const int f = p.splits > 1 ? -2 : (p.wide ? p.flags : -1);  // -2: split-K partial sums (the fold kernel applies the epilogue)
     const dim3 grid((unsigned)nwg, ns);
     switch (f) {
-#define AFK_CASE(F)                                                                                                   \
-    case (F):                                                                                                         \
-        if ((F) == -1) afk_count(AFK_CNT_GEMM_GENERIC);                                                               \
-        if (trans_a) hipLaunchKernelGGL((gemm_xt_bf16_k256<true, (F)>), grid, dim3(512), LDS_BYTES, st, p);          \
-        else hipLaunchKernelGGL((gemm_xt_bf16_k256<false, (F)>), grid, dim3(512), LDS_BYTES, st, p);                 \
+#define AFK_CASE(F)                                                                                        \
+    case (F):                                                                                              \
+        if ((F) == -1) afk_count(AFK_CNT_GEMM_GENERIC);                                                    \
+        hipLaunchKernelGGL((gemm_xt_bf16_k256<AT, (F), MF>), grid, dim3(512), LDS_BYTES, st, p);           \
         break;
         AFK_EPI_LIST(AFK_CASE)
 #undef AFK_CASE
         default:   // an epilogue outside the list: runtime-flag instantiation
             afk_count(AFK_CNT_GEMM_GENERIC);
-            if (trans_a) hipLaunchKernelGGL((gemm_xt_bf16_k256<true, -1>), grid, dim3(512), LDS_BYTES, st, p);
-            else hipLaunchKernelGGL((gemm_xt_bf16_k256<false, -1>), grid, dim3(512), LDS_BYTES, st, p);
+            hipLaunchKernelGGL((gemm_xt_bf16_k256<AT, -1, MF>), grid, dim3(512), LDS_BYTES, st, p);
     }
     return AFK_OK;
+}
+
+int afk_launch_gemm256t(const GemmArgs& p, int trans_a, int mf, hipStream_t st) {
+    if (trans_a) {
+        if constexpr ((AFK_MFMA_SHAPES_TN & 2) != 0)
+            if (mf == 16) return launch_gemm256t<true, 16>(p, st);
+        if constexpr ((AFK_MFMA_SHAPES_TN & 1) != 0)
+            if (mf == 32) return launch_gemm256t<true, 32>(p, st);
+    } else {
+        if constexpr ((AFK_MFMA_SHAPES_NN & 2) != 0)
+            if (mf == 16) return launch_gemm256t<false, 16>(p, st);
+        if constexpr ((AFK_MFMA_SHAPES_NN & 1) != 0)
+            if (mf == 32) return launch_gemm256t<false, 32>(p, st);
+    }
+    return afk_set_error(AFK_ERR_UNSUPPORTED, "gemm256t: the %s MFMA shape of the %s kernel is built under make PROBES=1 only", mf == 16 ? "16x16x32" : "32x32x16",
+                         trans_a ? "TN" : "NN");
 }

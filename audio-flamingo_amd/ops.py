@@ -849,6 +849,17 @@ def gemm_set_variant(v: int):
     _lib.call("afk_gemm_set_variant", int(v))
 
 
+def gemm_set_mfma(v: int):
+    """MFMA shape of the 256x256 kernels: 0 = the dispatch rule, 1 = 32x32x16, 2 = 16x16x32 (tests / A-B measurements; env AFK_GEMM_MFMA for a whole run)"""
+    _lib.call("afk_gemm_set_mfma", int(v))
+
+
+def gemm_mfma_shapes(form: str) -> tuple:
+    """which of the shapes (1 = 32x32x16, 2 = 16x16x32) the loaded library carries for form "nt" | "nn" | "tn" (the other one: make PROBES=1)"""
+    mask = _lib.load().afk_gemm_mfma_shapes(("nt", "nn", "tn").index(form))
+    return tuple(v for v in (1, 2) if mask >> (v - 1) & 1)
+
+
 # ---------------------------------------------------------------------------------------------- profiling
 KERNEL_FAMILIES = ("gemm_nt128", "gemm_nt256", "gemm_nn256", "gemm_tn256", "gemm_splitk", "gemv", "attn2_fwd_d64", "attn2_fwd_d128",
                    "attn2_bwd_d64", "attn2_bwd_d128", "gqa_reduce", "xattn_fwd", "xattn_bwd", "attn1_fwd", "attn1_bwd", "gemm_generic_epilogue")

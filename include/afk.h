@@ -70,6 +70,14 @@ int afk_prof_dump(const char* host_path);
  * stores (same results); + 256 * g (g = 1..63) = rasterization group height.  Any other value selects a timing probe or a rejected schedule: those
  * exist only in -DAFK_PROBES builds (make PROBES=1) and are refused (AFK_ERR_ARG) by the default library. */
 int afk_gemm_set_variant(int variant);
+/* MFMA shape of the 256x256 kernels (NT, NN, TN): 0 = the dispatch rule (csrc/gemm.hip gemm_mfma_of), 1 = v_mfma_f32_32x32x16_bf16, 2 = v_mfma_f32_16x16x32_bf16.
+ * The environment variable AFK_GEMM_MFMA (0 | 1 | 2, read once at the first 256x256 launch) sets the same thing for a whole process; a call with v != 0
+ * overrides it.  A kernel carries the shape its per-shape measurements do not justify under make PROBES=1 only: forcing a shape no kernel of the build carries
+ * is refused here (AFK_ERR_ARG), a launch of a kernel that lacks the forced shape fails with AFK_ERR_UNSUPPORTED.  Results of the two shapes agree to fp32
+ * summation order (exactly, where every partial sum is exact). */
+int afk_gemm_set_mfma(int v);
+/* shapes form (0 = NT, 1 = NN, 2 = TN) was built with: bit 0 = 32x32x16, bit 1 = 16x16x32 */
+int afk_gemm_mfma_shapes(int form);
 #define AFK_GEMM_BIAS 1
 #define AFK_GEMM_GELU 2
 #define AFK_GEMM_RESIDUAL 4
@@ -517,7 +525,8 @@ int afk_cu_hog(int nblocks, int lds_bytes, const int* stop_flag, int64_t max_tic
  * LDS fragment traffic added (12 ds_read_b128 per segment from a 64 KiB LDS image of `operands`).  *host_flops (nullable) receives the flops
  * of the launch; time it with HIP events on `stream`.  sink: device float, never written in practice.  modes 2 / 3: issue pacing of ONE wave per SIMD
  * (4-wave workgroups) over four accumulators - round-robin (2) or each accumulator four times in a row (3: back-to-back dependent MFMAs);
- * sink[0] = shader cycles per MFMA, sink needs 2 floats. */
+ * sink[0] = shader cycles per MFMA, sink needs 2 floats.  modes 4 / 5: modes 0 / 1 on v_mfma_f32_16x16x32_bf16 (same waves, operand registers, ds_read_b128
+ * and FLOPs per segment). */
 int afk_mfma_ceiling(int mode, int nblocks, int iters, const void* operands, float* sink, double* host_flops, void* stream);
 
 /* ---- HIP streams with an explicit queue priority (round 6).  The training step runs on three streams: the critical path (forward, dgrad, attention,

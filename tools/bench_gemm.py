@@ -1,5 +1,7 @@
 """GEMM microbenchmark on the AF3-7B shapes (random data, guide rule 25): the two 256x256 NT kernels (v2 = 8-wave ping-pong, v3 = 4-wave
-128x128 per wave), HIP-event timed through afk_prof_*.   python tools/bench_gemm.py [zeros]   (zeros: zero-filled operands = DVFS probe)"""
+128x128 per wave), HIP-event timed through afk_prof_*.   python tools/bench_gemm.py [zeros]   (zeros: zero-filled operands = DVFS probe)
+    python tools/bench_gemm.py mfma [out.json]    the step's NT / NN / TN shapes on each MFMA shape the library carries (ops.gemm_set_mfma 1 = 32x32x16,
+    2 = 16x16x32), alternating shape by shape: 5 warm + 25 timed launches each, HIP events per launch -> median / min / max per row"""
 import sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -14,6 +16,56 @@ SHAPES = [  # (name, M, N, K)
     ("square 4096", 4096, 4096, 4096), ("square 8192", 8192, 8192, 8192),
 ]
 dev = torch.device("cuda")
+
+
+def mfma_ab(out_path):
+    """per-shape A/B of the MFMA shapes (profiles/gemm_mfma_shape_ab.md table (c))"""
+    import statistics
+    rows = [("nt", n, M, N, K) for n, M, N, K in SHAPES[:4] + SHAPES[7:8] + SHAPES[10:14]]
+    rows += [("nn", "dec gate_up dgrad", 8192, 3584, 37888), ("nn", "dec down dgrad", 8192, 18944, 3584), ("nn", "dec qkv dgrad", 8192, 3584, 4608),
+             ("nn", "dec o dgrad", 8192, 3584, 3584), ("nn", "lm_head dgrad", 2048, 3584, 152064), ("nn", "enc fc1 dgrad", 12000, 1280, 5120), ("nn", "enc qkv dgrad", 12000, 1280, 3840),
+             ("tn", "dec gate_up wgrad", 37888, 3584, 8192), ("tn", "dec down wgrad", 3584, 18944, 8192), ("tn", "dec qkv wgrad", 4608, 3584, 8192),
+             ("tn", "dec o wgrad", 3584, 3584, 8192), ("tn", "lm_head wgrad", 152064, 3584, 2048), ("tn", "enc fc1 wgrad", 5120, 1280, 12000),
+             ("tn", "enc qkv wgrad", 3840, 1280, 12000), ("tn", "enc out wgrad", 1280, 1280, 12000)]
+    res = []
+    ops.gemm_set_variant(2)
+    try:
+        for form, name, M, N, K in rows:
+            a = torch.randn((K, M) if form == "tn" else (M, K), device=dev).to(torch.bfloat16)
+            b = torch.randn((N, K) if form == "nt" else (K, N), device=dev).to(torch.bfloat16)
+            c = torch.empty((M, N), device=dev, dtype=torch.bfloat16)
+            run = (lambda: ops.gemm_nt(a, b, out=c)) if form == "nt" else (lambda: ops.gemm(a, b, out=c, trans_a=form == "tn", trans_b=True))
+            shapes = ops.gemm_mfma_shapes(form)
+            ev = {v: [] for v in shapes}
+            for it in range(30):          # 5 warm + 25 timed, the shapes alternating launch by launch
+                for v in shapes:
+                    ops.gemm_set_mfma(v)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(); run(); e1.record()
+                    if it >= 5:
+                        ev[v].append((e0, e1))
+            torch.cuda.synchronize()
+            row = {"form": form, "name": name, "M": M, "N": N, "K": K}
+            for v in shapes:
+                us = sorted(1e3 * x.elapsed_time(y) for x, y in ev[v])
+                row[f"mfma{v}_us"] = {"median": round(statistics.median(us), 1), "min": round(us[0], 1), "max": round(us[-1], 1)}
+                row[f"mfma{v}_tflops"] = round(2.0 * M * N * K / statistics.median(us) / 1e6, 1)
+            if len(shapes) == 2:
+                row["speedup_2_over_1"] = round(row["mfma1_us"]["median"] / row["mfma2_us"]["median"], 4)
+            res.append(row)
+            print(json.dumps(row), flush=True)
+            del a, b, c
+    finally:
+        ops.gemm_set_mfma(0)
+        ops.gemm_set_variant(0)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        json.dump({"device": torch.cuda.get_device_name(0), "rows": res}, open(out_path, "w"), indent=1)
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "mfma":
+    mfma_ab(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
 ZEROS = len(sys.argv) > 1 and sys.argv[1] == "zeros"
 if len(sys.argv) > 1 and sys.argv[1] == "nt":
     SHAPES = SHAPES[:12] + SHAPES[-2:]

@@ -1,6 +1,7 @@
 """Ceiling of the matrix pipe under the socket power cap: afk_mfma_ceiling mode 0 (register-resident N(0,1) operands, no memory
-access in the loop) and mode 1 (+ the 256x256 GEMM's LDS fragment reads), ~2 s each on all 256 CUs x 8 waves, with clock and socket power sampled
-from sysfs / rocm-smi beside it; then the GEMM itself on the gate|up shape on N(0,1) operands and on zeros.
+access in the loop) and mode 1 (+ the 256x256 GEMM's LDS fragment reads), and the same two loops on v_mfma_f32_16x16x32_bf16 (modes 4 / 5), ~2 s each
+on all 256 CUs x 8 waves, with clock and socket power sampled from sysfs / rocm-smi beside it; then the GEMM itself on the gate|up shape on N(0,1)
+operands (once per MFMA shape the library carries) and on zeros.
     python tools/measure_mfma_ceiling.py [out.json]        -> profiles/r06_mfma_power_ceiling.md is written from this"""
 import ctypes
 import glob
@@ -91,7 +92,9 @@ def main():
     sink = torch.zeros(4, device=dev)
     out = {"afk_build_id": _lib.load().afk_build_id().decode(), "device": torch.cuda.get_device_name(0), "legs": {}}
     stream = torch.cuda.current_stream().cuda_stream
-    for name, mode, operands in (("mfma_registers_n01", 0, seed), ("mfma_lds_reads_n01", 1, seed), ("mfma_registers_zeros", 0, torch.zeros_like(seed))):
+    zeros = torch.zeros_like(seed)
+    for name, mode, operands in (("mfma_registers_n01", 0, seed), ("mfma16_registers_n01", 4, seed), ("mfma_lds_reads_n01", 1, seed), ("mfma16_lds_reads_n01", 5, seed),
+                                 ("mfma_registers_zeros", 0, zeros), ("mfma16_registers_zeros", 4, zeros)):
         fl = ctypes.c_double(0)
         iters = 20000     # 256 blocks x 8 waves x 20000 x 16 MFMAs = 21.5 TFLOP per launch (~12 ms at 1.8 PF)
 
@@ -104,8 +107,13 @@ def main():
     a = torch.randn(8192, 3584, device=dev).to(torch.bfloat16)
     w = torch.randn(37888, 3584, device=dev).to(torch.bfloat16)
     c = torch.empty((8192, 37888), device=dev, dtype=torch.bfloat16)
-    for name, A, W in (("gemm_gate_up_n01", a, w), ("gemm_gate_up_zeros", torch.zeros_like(a), torch.zeros_like(w))):
-        ms, n, smp = timed(lambda: ops.gemm_nt(A, W, out=c), 2.0)
+    legs = [("gemm_gate_up_n01", a, w, 0)] + [(f"gemm_gate_up_n01_mfma{v}", a, w, v) for v in ops.gemm_mfma_shapes("nt")]
+    for name, A, W, shape in legs + [("gemm_gate_up_zeros", torch.zeros_like(a), torch.zeros_like(w), 0)]:
+        ops.gemm_set_mfma(shape)
+        try:
+            ms, n, smp = timed(lambda: ops.gemm_nt(A, W, out=c), 2.0)
+        finally:
+            ops.gemm_set_mfma(0)
         out["legs"][name] = {"tflops": 2.0 * 8192 * 37888 * 3584 * n / (ms * 1e-3) / 1e12, "ms_per_launch": ms / n, "launches": n, **smp}
         print(name, json.dumps(out["legs"][name]), flush=True)
         time.sleep(1.0)

@@ -196,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_bf16_f8(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) gemm_store_block32(p, m0 + wm * 128 + i * 32 + l31, n0 + wn * 64 + j * 32, hi, acc[i][j]);
+        for (int j = 0; j < 2; ++j) gemm_store_block32(p, m0 + wm * 128 + i * 32, n0 + wn * 64 + j * 32, lane, acc[i][j]);
     if constexpr (MODE == 2) {
         // block timeline in s_memrealtime ticks (100 MHz): entry, prologue done, loop done, stores retired; + hardware id (CU) of the block
         uint64_t rt_end;

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256p(GemmArgs p_in) {
     if (!AFK_GM_NOEPI(pe))  // bit 6 of gm (afk_gemm_set_variant(13 + 256 * 0x40)): timing probe WITHOUT the epilogue (wrong results) - profiles/r02_gemm_probes.md §9
     afk_static_for<8>([&](auto ij_) {  // compile-time indices: inside the tile loop a #pragma unroll was not honoured and acc went through scratch
         constexpr int i = decltype(ij_)::value >> 1, j = decltype(ij_)::value & 1;
-        gemm_store_block32(pe, m0 + wm * 128 + i * 32 + l31, n0 + wn * 64 + j * 32, hi, acc[i][j]);
+        gemm_store_block32(pe, m0 + wm * 128 + i * 32, n0 + wn * 64 + j * 32, lane, acc[i][j]);
     });
   }  // tile loop
 }

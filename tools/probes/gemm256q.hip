@@ -201,7 +201,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256q(GemmArgs p_in) {
         }
         afk_static_for<8>([&](auto ij_) {
             constexpr int i = decltype(ij_)::value >> 1, j = decltype(ij_)::value & 1;
-            gemm_store_block32_body<0>(pe, em0 + wm * 128 + i * 32 + l31, en0 + wn * 64 + j * 32, hi, acc[i][j]);
+            gemm_store_block32_body<0, 32>(pe, em0 + wm * 128 + i * 32, en0 + wn * 64 + j * 32, lane, acc[i][j]);
         });
         if (!more) break;
         if (em0 + BM > pe.M || en0 + BN > pe.N) AFK_VMCNT(0);   // ragged tile: fewer than 16 stores may have been issued - the raised waits need exactly 16

@@ -235,7 +235,7 @@ __global__ __launch_bounds__(JT == 4 ? 256 : 512, JT == 4 ? 1 : 2) void gemm_nt_
     // (one 32x32 block at a time, fenced: left alone the compiler hoists all accumulator reads to the top and spills ~160 VGPRs)
     afk_static_for<4 * JT>([&](auto ij_) {
         constexpr int i = decltype(ij_)::value / JT, j = decltype(ij_)::value % JT;
-        gemm_store_block32(p, m0 + wm * 128 + i * 32 + l31, n0 + wn * 32 * JT + j * 32, hi, acc[i][j]);
+        gemm_store_block32(p, m0 + wm * 128 + i * 32, n0 + wn * 32 * JT + j * 32, lane, acc[i][j]);
         __builtin_amdgcn_sched_barrier(0);
     });
 }
