@@ -24,7 +24,8 @@ Deviations from the oracle surface (documented, not silent):
   * ``generate``: prefill fills a KV cache, each new token is one HIP-graph replay; greedy by default, ``do_sample=True`` with
     ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` (the reference's logits-warper order, drawn on the device by ``afk_decode_sample`` inside the
     replayed step: the ids are a function of the seed, not of torch's generator stream; top-p keeps a class of equal logits whole), or ``num_beams > 1`` (beam search with the
-    reference's scoring); ``generation_config`` supplies defaults; constrained / assisted decoding and custom logits processors are not built;
+    reference's scoring); ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens`` / ``suppress_tokens`` / ``begin_suppress_tokens`` are applied
+    on the device inside the replayed step (``afk_decode_process``, decode_process.py); ``generation_config`` supplies defaults; constrained / assisted decoding are not built;
   * ``attention_mask`` rows must be one contiguous run of ones (left padding - the reference processor's default -, right padding, or
     both); masks with holes raise.  Hidden states of padded positions are zeros-attended garbage in both implementations and are
     never compared.
@@ -39,6 +40,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops
+from . import decode_process as _process
 from ._lib import AfkError
 from .arena import Arena
 from . import functional as F_
@@ -1021,10 +1023,17 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             wd = A("mlp.down_proj.weight").data
             x = torch.empty_like(x2)
             _lib.call("afk_decode_chain_linear_residual", act.data_ptr(), wd.data_ptr(), wd.stride(0), H, I, x2.data_ptr(), x.data_ptr(), st)
-        if greedy is not None and greedy.get("sampling"):   # sampled: the lm_head launch writes the fp32 logits, the sample launch draws and does the bookkeeping
+        if greedy is not None and (greedy.get("sampling") or greedy.get("proc")):
+            # sampled, or logits processors: the lm_head launch writes the fp32 logits; the processors' launch edits the row (and, greedy, selects from it and
+            # does the bookkeeping); the sample launch draws and does the bookkeeping
             g = greedy
             _lib.call("afk_decode_chain_lm_head", x.data_ptr(), a[lm + "norm.weight"].data.data_ptr(), eps, head.data_ptr(), head.stride(0), head.shape[0], H,
                       g["logits"].data_ptr(), None, None, st)
+            if g.get("proc"):
+                sel = {} if g.get("sampling") else dict(select=True, tokens_out=g["tok_buf"], tok_off=g["tok_off"], state=g["state"], emb=g["emb"], x_out=g["x0"])
+                _process.apply(g["proc"], g["logits"], next_token=g["nxt"], step_base=g["cur"], step_off=g["tok_off"], **sel)
+                if sel:
+                    return None
             self._sample_token(g["logits"], g["sampling"], step_base=g["cur"], step_off=g["tok_off"], out=g["nxt"], tokens_out=g["tok_buf"], tok_off=g["tok_off"],
                                state=g["state"], emb=g["emb"], x_out=g["x0"])
             return None
@@ -1189,10 +1198,13 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         if "x0" in st:   # one sequence: 5 launches per layer + lm_head + ONE launch for argmax or the draw / token / positions / the next embedding row
             self._decode_layers_chain(st["x0"], st["cache"], st["pos1"], st["kr1"], st["cur"], aws=st["aws"], head=st["head"], greedy=st)
             return
-        if st.get("sampling"):   # the token being generated is number cur + 1 - S0: the draw's counter lives on the device and advances with the step
-            self._sample_token(self._decode_logits(st), st["sampling"], step_base=st["cur"], step_off=st["tok_off"], out=st["nxt"])
+        logits = self._decode_logits(st)
+        if st.get("proc"):   # the token being generated is number cur + 1 - S0: the processors' (and the draw's) counter lives on the device and advances with the step
+            _process.apply(st["proc"], logits, next_token=st["nxt"], step_base=st["cur"], step_off=st["tok_off"])
+        if st.get("sampling"):
+            self._sample_token(logits, st["sampling"], step_base=st["cur"], step_off=st["tok_off"], out=st["nxt"])
         else:
-            st["nxt"].copy_(self._select_token(self._decode_logits(st)))
+            st["nxt"].copy_(self._select_token(logits))
         (st["advance"] if "advance" in st else st["cur"]).add_(1)   # single sequence: cur, position and the key-range end live in one tensor (generate())
 
     @torch.no_grad()
@@ -1327,13 +1339,22 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, input_features=None, input_features_mask=None, attention_mask=None, max_new_tokens=20,
                  do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, eos_token_id=None, pad_token_id=None, use_cache=True,
-                 use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, **kwargs):
+                 use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, repetition_penalty=1.0,
+                 no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, **kwargs):
         """Greedy decoding, sampling or beam search (GenerationMixin.generate, transformers/generation/utils.py; do_sample with temperature /
         top_k / top_p as its logits warpers apply them, drawn on the device by afk_decode_sample from a counter-based generator: seed (64 bits; None: from
         torch.seed()) and the index of the token are all the state there is, so a seed gives the same ids in eager, graph-replayed and hook-driven loops; num_beams > 1: beam search with the
         reference's scoring - accumulated log-probabilities, finished hypotheses ranked by sum / length^length_penalty, its early-stop
         heuristic).  generation_config (a transformers.GenerationConfig or anything with the same attributes) supplies defaults for the
-        arguments left at theirs, as GenerationMixin merges them.  Cache handling as
+        arguments left at theirs, as GenerationMixin merges them.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens: the logits processors
+        GenerationMixin._get_logits_processor puts in front of the warpers, with its validation (decode_process.resolve), applied in its order by ONE launch per
+        step (afk_decode_process) on a device-resident id history - the prompt ids as passed, padding and <sound> ids included, then every selected token - so
+        greedy and sampled steps still replay in the decode graph; user `logits_processor`s run after them, as the reference appends them.  With none of them
+        active nothing extra is enqueued.  They are refused with num_beams > 1 and with use_cache=False.  Not covered (refused as keywords, ignored in a
+        generation config as before): bad_words_ids (its reference class adds a bias to the whole row and handles multi-token sequences; single ids are what
+        suppress_tokens does); min_p / typical_p / epsilon_cutoff / eta_cutoff / top_h (they belong behind top-p in the sampler); forced_eos_token_id,
+        encoder_*, sequence_bias, exponential_decay_length_penalty.  Cache handling as
         Qwen2Attention.forward modeling_qwen2.py:213-214).  Prefill runs the prompt once and fills a per-layer KV cache; every new
         token then costs one pass over the weights and one Q=1 attention over the cache.  Batches may be LEFT padded
         (attention_mask, as the processor pads): positions count real tokens only and padded keys are never visible.
@@ -1355,11 +1376,16 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             do_sample, temperature, top_k, top_p = pick(do_sample, False, "do_sample"), pick(temperature, 1.0, "temperature"), pick(top_k, 50, "top_k"), pick(top_p, 1.0, "top_p")
             num_beams, length_penalty, early_stopping = pick(num_beams, 1, "num_beams"), pick(length_penalty, 1.0, "length_penalty"), pick(early_stopping, False, "early_stopping")
             eos_token_id, pad_token_id = pick(eos_token_id, None, "eos_token_id"), pick(pad_token_id, None, "pad_token_id")
+        spec = _process.resolve(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, begin_suppress_tokens, eos_token_id=eos_token_id,
+                                generation_config=gc)   # the five logits processors: keyword, else generation config, validated as the reference does
         from . import exact as _exact
 
         if int(max_new_tokens) <= 0:   # GenerationMixin refuses it as well (generation/configuration_utils.py validate())
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
-        if _exact.ENABLED and not do_sample and num_beams == 1 and not hooks and type(self).__name__ == "AudioFlamingo3ForConditionalGeneration":
+        if spec.active and (num_beams > 1 or not use_cache):
+            raise AfkError("generate(repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens): greedy or sampled "
+                           "decoding on the KV cache only (no num_beams > 1, no use_cache=False)")
+        if _exact.ENABLED and not do_sample and num_beams == 1 and not hooks and not spec.active and type(self).__name__ == "AudioFlamingo3ForConditionalGeneration":
             # AFK_EXACT_FP32=1: greedy decoding by exact-fp32 recomputation of the prefix (exact.py) - the reference's greedy ids with no "confident rows" filter
             return _exact.greedy_generate(self, input_ids, input_features, input_features_mask, attention_mask, max_new_tokens, eos_token_id, pad_token_id)
         if num_beams > 1 and (do_sample or not use_cache):
@@ -1401,10 +1427,14 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         if num_beams > 1:
             return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), int(max_new_tokens), eos_token_id, pad_token_id, float(length_penalty), early_stopping)
         first_logits = ops.gemm_nt(last, self.arena["lm_head.weight"].data).float()
+        proc = None
+        if spec.active:   # token 0, eagerly, with the kernel of the captured steps; in front of the user's processors (GenerationMixin._merge_criteria_processor_list)
+            proc = _process.build_state(spec, ids, int(max_new_tokens), first_logits.shape[1])
+            _process.apply(proc, first_logits)
         if procs:
             first_logits = procs(ids, first_logits)
         st = {"cache": (Kc, Vt), "lo": lo, "head": self.arena["lm_head.weight"].data, "emb": self.arena[self._lm + "embed_tokens.weight"].data,
-              "cur": torch.full((1,), S0, device=dev, dtype=torch.int32), "sampling": sampling, "tok_off": 1 - S0,
+              "cur": torch.full((1,), S0, device=dev, dtype=torch.int32), "sampling": sampling, "tok_off": 1 - S0, "proc": proc,
               "nxt": self._sample_token(first_logits, sampling) if sampling else self._select_token(first_logits)}   # the first token is draw 0
         if B == 1:   # one device tensor [lo, key-range end, cache slot, position] -> the views the kernels read; one add per step moves the last three
             state = torch.cat([lo, torch.tensor([S0 + 1, S0], device=dev, dtype=torch.int32), S0 - lo]).contiguous()
@@ -1413,7 +1443,7 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
                 tok_buf = torch.zeros(max_new_tokens, device=dev, dtype=torch.int64)
                 tok_buf[0] = st["nxt"][0]
                 st.update(x0=st["emb"].index_select(0, st["nxt"]).contiguous(), aws=self._decode_attn_workspace(dev, Vt.shape[4]), tok_buf=tok_buf)
-                if sampling:
+                if sampling or proc:
                     st.update(logits=torch.empty((1, st["head"].shape[0]), device=dev, dtype=torch.float32))
                 else:
                     st.update(part_val=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.float32),
@@ -1467,6 +1497,8 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             if t > 0:
                 logits = self._decode_logits(st)        # appends the K / V of st["nxt"] at the cache slot st["cur"]
                 (st["advance"] if "advance" in st else st["cur"]).add_(1)
+                if st.get("proc"):   # the built-in processors first: st["nxt"] is token t - 1 as appended to seq (pad for a finished row)
+                    _process.apply(st["proc"], logits, next_token=st["nxt"], step_off=t)
                 if procs:
                     logits = procs(seq, logits)
             tok = self._sample_token(logits, st["sampling"], step_off=t) if st.get("sampling") else self._select_token(logits)

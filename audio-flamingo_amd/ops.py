@@ -757,6 +757,47 @@ def decode_sample(logits, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, u=None
     return out
 
 
+def decode_process(logits, hist, seen, *, S0, penalty=1.0, ngram=0, suppress=None, begin_suppress=None, eos=None, min_new_tokens=0, next_token=None,
+                   step_base=None, step_off=0, select=False, tokens_out=None, tok_off=0, state=None, emb=None, x_out=None):
+    """the fp32 logits [B, V] processed IN PLACE for token t = *step_base + step_off: repetition penalty -> no-repeat n-gram -> eos / suppress / begin-suppress bans
+    in one launch (afk_decode_process; the contract is in include/afk.h).  hist [B, ld] int32: the S0 prompt ids then the selected tokens; seen [B, ld_seen] int32:
+    one bit per vocabulary id of the row's history (decode_process.build_state fills both from the prompt); next_token [B] int64: the token selected for t - 1,
+    appended by the launch (only token 0 has none).  suppress / begin_suppress / eos: int32 id lists on the device.  select (B == 1; state, emb, x_out, and
+    tokens_out / tok_off): greedy selection from the processed row and the step bookkeeping of afk_decode_select_greedy in the same launch.  -> logits"""
+    _chk(logits, torch.float32, "decode_process logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise AfkError(f"decode_process logits: [B, V] with unit column stride, got {tuple(logits.shape)} strides {logits.stride()}")
+    B, V = logits.shape
+    for t_, name, cols in ((hist, "hist", int(S0)), (seen, "seen", (V + 31) // 32)):
+        _chk(t_, torch.int32, f"decode_process {name}")
+        if t_.dim() != 2 or t_.shape[0] != B or t_.stride(1) != 1 or t_.shape[1] < cols:
+            raise AfkError(f"decode_process {name}: [{B}, >= {cols}] with unit column stride, got {tuple(t_.shape)} strides {t_.stride()}")
+    for t_, dt, n, name in ((next_token, torch.int64, B, "next_token"), (step_base, torch.int32, 1, "step_base"), (tokens_out, torch.int64, 1, "tokens_out"),
+                            (state, torch.int32, 4, "state"), (suppress, torch.int32, 0, "suppress"), (begin_suppress, torch.int32, 0, "begin_suppress"),
+                            (eos, torch.int32, 0, "eos")):
+        if t_ is not None:
+            _chk(t_, dt, f"decode_process {name}")
+            if t_.numel() < n or not t_.is_contiguous():
+                raise AfkError(f"decode_process {name}: a contiguous tensor of at least {n} elements, got {tuple(t_.shape)}")
+    if next_token is None and (step_base is not None or step_off != 0 or select):
+        raise AfkError("decode_process: next_token (the token selected for t - 1) is needed for every token but token 0 without selection")
+    H = 0
+    if select:
+        if state is None or emb is None or x_out is None:
+            raise AfkError("decode_process: select needs state, emb and x_out (the embedding row of the token is the next step's input)")
+        _chk(emb, BF16, "decode_process emb"), _chk(x_out, BF16, "decode_process x_out")
+        H = emb.shape[1]
+        if x_out.numel() < H or not x_out.is_contiguous() or V > emb.shape[0]:
+            raise AfkError(f"decode_process: x_out holds {x_out.numel()} elements, emb is {tuple(emb.shape)} for V = {V}")
+    n_of = lambda t_: 0 if t_ is None else t_.numel()
+    _lib.call("afk_decode_process", logits.data_ptr(), logits.stride(0), B, V, hist.data_ptr(), hist.stride(0), int(S0), seen.data_ptr(), seen.stride(0),
+              _p(step_base), int(step_off), _p(next_token), float(penalty), int(ngram), _p(suppress) if n_of(suppress) else None, n_of(suppress),
+              _p(begin_suppress) if n_of(begin_suppress) else None, n_of(begin_suppress), _p(eos) if n_of(eos) else None, n_of(eos), int(min_new_tokens),
+              1 if select else 0, _p(tokens_out) if select else None, int(tok_off), _p(state) if select else None, _p(emb) if select else None,
+              emb.stride(0) if select else 0, H, _p(x_out) if select else None, _stream())
+    return logits
+
+
 # ---------------------------------------------------------------------------------------------- loss
 def count_valid(labels):
     out = torch.empty(1, device=labels.device, dtype=torch.float32)

@@ -395,6 +395,29 @@ int afk_decode_select_greedy(const float* part_val, const int* part_idx, int npa
 int afk_decode_sample(const float* logits, int64_t ld_logits, int B, int V, float temperature, int top_k, float top_p, const float* u, int64_t seed,
                       const int* step_base, int step_off, int64_t* next_token, float* probs_out, int64_t ld_probs, int* kept_out, int64_t* tokens_out, int tok_off,
                       int* state, const void* emb, int64_t ld_emb, int H, void* x_out, void* stream);
+/* Logits processors on the device (csrc/decode_process.hip), one launch for B rows of fp32 logits [B][V] (row stride ld_logits >= V; any V >= 1, any B >= 1),
+ * processed IN PLACE: the processors GenerationMixin._get_logits_processor (transformers/generation/utils.py:1174-1290) puts in front of the warpers, in its order -
+ * RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor, MinNewTokensLengthLogitsProcessor, SuppressTokensLogitsProcessor,
+ * SuppressTokensAtBeginLogitsProcessor (transformers/generation/logits_process.py) - with no host state: enqueue-only, no allocation, capturable.
+ * t = *step_base + step_off = the index of the token being selected (step_base: device int32, null = 0; the convention of afk_decode_sample).  What the reference
+ * reads from input_ids is on the device: hist [B][ld_hist] int32 = the S0 prompt ids as passed to generate (padding and <sound> ids included) followed by the
+ * selected tokens, seen [B][ld_seen] = one bit per vocabulary id (bit id % 32 of word id / 32) that occurs in the row's history; the caller fills hist[:, :S0] and
+ * the bits of the prompt once.  Per row:
+ *   0. t >= 1: hist[b][S0 + t - 1] = next_token[b] (the token selected for t - 1) and its bit is set; the history is then the n = S0 + t ids hist[b][0 .. n).
+ *      Storing the same token twice changes nothing, so an eager rerun or a graph replay of the same step is harmless.
+ *   1. repetition penalty (:409-412): every id of the seen set ONCE, however often it occurs: x = x < 0 ? x * penalty : x / penalty in fp32 (IEEE * and /).
+ *   2. no-repeat n-gram (:1117-1140), g = no_repeat_ngram_size > 0 and n + 1 >= g: for every j in [0, n - g] whose g - 1 ids hist[j .. j + g - 2] equal the last
+ *      g - 1 ids of the history, logits[hist[j + g - 1]] = -inf (g == 1 bans every id of the history; a history shorter than g - 1 bans nothing).
+ *   3. logits[id] = -inf for the suppress ids always, the begin_suppress ids when t == 0, and the eos ids when t < min_new_tokens.
+ * Ids outside [0, V) in the history or the lists are skipped (the reference raises on them).  select != 0 (B == 1 only): the launch also selects the greedy token of
+ * the processed row - ties resolve to the lowest id, a +inf wins at its lowest id, a row with no finite logit answers 0, NaN never wins: the rules of
+ * afk_decode_select_greedy - and does that entry's bookkeeping: next_token[0], tokens_out[state[2] + tok_off] (tokens_out may be null), state[1 .. 3] += 1,
+ * x_out[H] = emb[token][:H].  next_token may be null only for token 0 without selection.  penalty > 0, no_repeat_ngram_size >= 0, S0 + t <= ld_hist (checked
+ * where the host knows t, i.e. step_base == null; a launch that would pass the buffer on the device appends and marks nothing and reads hist[b][0 .. ld_hist)). */
+int afk_decode_process(float* logits, int64_t ld_logits, int B, int V, int* hist, int64_t ld_hist, int S0, unsigned int* seen, int64_t ld_seen,
+                       const int* step_base, int step_off, int64_t* next_token, float penalty, int no_repeat_ngram_size, const int* suppress, int n_suppress,
+                       const int* begin_suppress, int n_begin_suppress, const int* eos, int n_eos, int min_new_tokens, int select, int64_t* tokens_out,
+                       int tok_off, int* state, const void* emb, int64_t ld_emb, int H, void* x_out, void* stream);
 /* The same launches for 2 .. 8 sequences decoded together (one new position each; the weights are still read once per step): M input rows h [M][K] (row stride
  * ldh) that are ALREADY normalised where the Linear follows a norm (Qwen2DecoderLayer :270 / :294, Qwen2Model.norm); pos[M] = position of each sequence's new token,
  * *start_dev = the cache slot all of them write; q_out [M][Hq*D] (row stride ldq); k_bs / vt_bs = batch strides of the K / V^T caches (elements).  Rounding points as above. */
