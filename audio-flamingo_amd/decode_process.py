@@ -5,11 +5,13 @@ step (afk_decode_process, csrc/decode_process.hip; the contract is in include/af
   resolve(...)      pure, CPU-runnable: merges the keywords with a generation config, validates as the reference does -> ProcessSpec
   build_state(...)  the device state of a prompt batch: id history, seen-set bitmap, id lists
   apply(...)        one launch on a [B, V] fp32 logits row block
+  resolve_warpers(...)  pure, CPU-runnable: min_p / typical_p / epsilon_cutoff / eta_cutoff merged and validated the same way.  These four are no processors of
+                    this file's launch: they sit behind top-p inside the sampler (afk_decode_sample_filtered, csrc/decode_sample.hip), where generate() sends them
 
 Deliberately not covered (generate() keeps refusing them as keywords; in a generation config they stay ignored, as before):
   * bad_words_ids - its reference class adds a bias tensor to the whole row (which turns -0.0 into +0.0) and handles multi-token sequences; single ids are what
     suppress_tokens does;
-  * min_p, typical_p, epsilon_cutoff, eta_cutoff, top_h - they sit behind top-p inside the sampler (csrc/decode_sample.hip);
+  * top_h - its warper sits in front of top-k inside the sampler and is a sequential scan;
   * forced_eos_token_id, encoder_repetition_penalty / encoder_no_repeat_ngram_size, sequence_bias, exponential_decay_length_penalty."""
 from __future__ import annotations
 
@@ -76,6 +78,39 @@ def resolve(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, su
     eos = _id_list(eos_token_id, "eos_token_id")
     return ProcessSpec(penalty=float(p), ngram=int(g), min_new_tokens=int(mn) if eos else 0, eos=eos if mn > 0 else (),
                        suppress=_id_list(kw["suppress_tokens"], "suppress_tokens"), begin_suppress=_id_list(kw["begin_suppress_tokens"], "begin_suppress_tokens"))
+
+
+WARPER_DEFAULTS = dict(min_p=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0)
+WARPERS_OFF = dict(min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0)
+
+
+def resolve_warpers(min_p=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, generation_config=None, do_sample=True) -> dict:
+    """keywords (+ a generation config for the ones left at their default; an explicit keyword wins) -> the four values as ops.decode_sample takes them, an
+    inactive filter at its "off" value.  As GenerationMixin._get_logits_processor gates them (utils.py:1323-1343): min_p whenever it is set, typical_p when
+    < 1, epsilon_cutoff / eta_cutoff only inside (0, 1); the classes' own validation and wording (MinPLogitsWarper / TypicalLogitsWarper.__init__): min_p
+    outside [0, 1] and typical_p <= 0 raise ValueError.  do_sample=False: nothing is built, so nothing is validated and all four are off."""
+    kw = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+    gc = generation_config
+    if gc is not None:
+        for k in kw:
+            if kw[k] == WARPER_DEFAULTS[k] and getattr(gc, k, None) is not None:
+                kw[k] = getattr(gc, k)
+    out = dict(WARPERS_OFF)
+    if not do_sample:
+        return out
+    if kw["min_p"] is not None:
+        if not (0 <= kw["min_p"] <= 1.0):
+            raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {kw['min_p']}")
+        out["min_p"] = float(kw["min_p"])
+    if kw["typical_p"] is not None and kw["typical_p"] < 1.0:
+        mass = float(kw["typical_p"])
+        if not (mass > 0 and mass < 1):
+            raise ValueError(f"`typical_p` has to be a float > 0 and < 1, but is {mass}")
+        out["typical_p"] = mass
+    for k in ("epsilon_cutoff", "eta_cutoff"):
+        if kw[k] is not None and 0.0 < kw[k] < 1.0:
+            out[k] = float(kw[k])
+    return out
 
 
 def build_state(spec: ProcessSpec, ids, max_new_tokens: int, V: int):

@@ -22,7 +22,8 @@ Deviations from the oracle surface (documented, not silent):
   * ``forward(use_cache=True)`` / ``forward(past_key_values=cache)``: the reference's cache protocol for inference (prefill returns an
     ``AfkKVCache``, later calls append one or several tokens); same kernels and cache layout as ``generate``;
   * ``generate``: prefill fills a KV cache, each new token is one HIP-graph replay; greedy by default, ``do_sample=True`` with
-    ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` (the reference's logits-warper order, drawn on the device by ``afk_decode_sample`` inside the
+    ``temperature`` / ``top_k`` / ``top_p`` / ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff`` / ``seed`` (the reference's logits-warper order,
+    filtered and drawn on the device by one launch, ``afk_decode_sample_filtered``, inside the
     replayed step: the ids are a function of the seed, not of torch's generator stream; top-p keeps a class of equal logits whole), or ``num_beams > 1`` (beam search with the
     reference's scoring); ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens`` / ``suppress_tokens`` / ``begin_suppress_tokens`` are applied
     on the device inside the replayed step (``afk_decode_process``, decode_process.py); ``generation_config`` supplies defaults; constrained / assisted decoding are not built;
@@ -1330,19 +1331,24 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
 
     @staticmethod
     def _sample_token(logits, sampling, **kw):
-        """the sampling chain of _select_token on the device, in one launch and with no host state (ops.decode_sample): temperature -> top-k -> top-p -> the
-        draw from a counter-based generator keyed by sampling["seed"]; kw: the draw's counter (step_base / step_off) and the outputs"""
+        """the sampling chain of _select_token on the device, in one launch and with no host state (ops.decode_sample): temperature -> top-k -> top-p ->
+        min_p -> typical_p -> epsilon_cutoff -> eta_cutoff -> the draw from a counter-based generator keyed by sampling["seed"]; kw: the draw's counter
+        (step_base / step_off) and the outputs.  Every sampled token of generate() - the first, the batched step, the one-sequence chain, the hook loop - comes
+        through here with the same `sampling` dict."""
         if logits.dtype != torch.float32 or logits.stride(-1) != 1:
             logits = logits.float().contiguous()
-        return ops.decode_sample(logits, temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"], seed=sampling["seed"], **kw)
+        return ops.decode_sample(logits, temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"], seed=sampling["seed"],
+                                 min_p=sampling["min_p"], typical_p=sampling["typical_p"], epsilon_cutoff=sampling["epsilon_cutoff"],
+                                 eta_cutoff=sampling["eta_cutoff"], **kw)
 
     @torch.no_grad()
     def generate(self, input_ids, input_features=None, input_features_mask=None, attention_mask=None, max_new_tokens=20,
                  do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, eos_token_id=None, pad_token_id=None, use_cache=True,
                  use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, repetition_penalty=1.0,
-                 no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, **kwargs):
+                 no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, min_p=None, typical_p=1.0,
+                 epsilon_cutoff=0.0, eta_cutoff=0.0, **kwargs):
         """Greedy decoding, sampling or beam search (GenerationMixin.generate, transformers/generation/utils.py; do_sample with temperature /
-        top_k / top_p as its logits warpers apply them, drawn on the device by afk_decode_sample from a counter-based generator: seed (64 bits; None: from
+        top_k / top_p / min_p / typical_p / epsilon_cutoff / eta_cutoff as its logits warpers apply them and in their order, drawn on the device by afk_decode_sample from a counter-based generator: seed (64 bits; None: from
         torch.seed()) and the index of the token are all the state there is, so a seed gives the same ids in eager, graph-replayed and hook-driven loops; num_beams > 1: beam search with the
         reference's scoring - accumulated log-probabilities, finished hypotheses ranked by sum / length^length_penalty, its early-stop
         heuristic).  generation_config (a transformers.GenerationConfig or anything with the same attributes) supplies defaults for the
@@ -1353,8 +1359,13 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         greedy and sampled steps still replay in the decode graph; user `logits_processor`s run after them, as the reference appends them.  With none of them
         active nothing extra is enqueued.  They are refused with num_beams > 1 and with use_cache=False.  Not covered (refused as keywords, ignored in a
         generation config as before): bad_words_ids (its reference class adds a bias to the whole row and handles multi-token sequences; single ids are what
-        suppress_tokens does); min_p / typical_p / epsilon_cutoff / eta_cutoff / top_h (they belong behind top-p in the sampler); forced_eos_token_id,
-        encoder_*, sequence_bias, exponential_decay_length_penalty.  Cache handling as
+        suppress_tokens does); top_h (its warper sits in front of top-k and is a sequential scan); forced_eos_token_id,
+        encoder_*, sequence_bias, exponential_decay_length_penalty.
+        min_p / typical_p / epsilon_cutoff / eta_cutoff run inside the sampler's launch behind top-p (afk_decode_sample_filtered), so a sampled step with them still
+        replays in the decode graph.  Gating and validation are the reference's (decode_process.resolve_warpers): min_p outside [0, 1] and typical_p <= 0 raise
+        ValueError, typical_p >= 1 and epsilon_cutoff / eta_cutoff outside (0, 1) are inactive, and do_sample=False ignores all four.  Left at their defaults they
+        are taken from the generation config like top_p - a config that carries one of them was ignored before and now changes the distribution sampled from, as
+        it does in the reference.  Cache handling as
         Qwen2Attention.forward modeling_qwen2.py:213-214).  Prefill runs the prompt once and fills a per-layer KV cache; every new
         token then costs one pass over the weights and one Q=1 attention over the cache.  Batches may be LEFT padded
         (attention_mask, as the processor pads): positions count real tokens only and padded keys are never visible.
@@ -1393,9 +1404,10 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         if hooks and (num_beams > 1 or not use_cache):
             raise AfkError("generate(logits_processor / stopping_criteria / streamer): greedy or sampled decoding on the KV cache only")
         sampling = None
+        warp = _process.resolve_warpers(min_p, typical_p, epsilon_cutoff, eta_cutoff, generation_config=gc, do_sample=bool(do_sample) and num_beams == 1)
         if do_sample and int(top_k or 0) != 1:   # top_k == 1 is greedy selection (and keeps the no-logits path)
             sampling = dict(temperature=float(temperature) if temperature else 1.0, top_k=int(top_k or 0), top_p=1.0 if top_p is None else float(top_p),
-                            seed=(int(seed) if seed is not None else int(torch.seed())) & (2 ** 64 - 1))
+                            seed=(int(seed) if seed is not None else int(torch.seed())) & (2 ** 64 - 1), **warp)
         ids = input_ids.to(self.device_)
         if not use_cache:
             if do_sample:

@@ -720,9 +720,9 @@ def scatter_rows(src, rows, M):
 
 # ---------------------------------------------------------------------------------------------- token sampling
 def decode_sample(logits, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, u=None, step_base=None, step_off=0, out=None, probs_out=None, kept_out=None,
-                  tokens_out=None, tok_off=0, state=None, emb=None, x_out=None):
-    """next_token [B] (int64) drawn from the fp32 logits [B, V]: temperature -> top-k -> top-p -> draw in one launch (afk_decode_sample; the contract is in
-    include/afk.h).  u [B] fp32 on the device supplies the uniforms; without it they come from Philox4x32-10 keyed by the 64-bit `seed`, counter
+                  tokens_out=None, tok_off=0, state=None, emb=None, x_out=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+    """next_token [B] (int64) drawn from the fp32 logits [B, V]: temperature -> top-k -> top-p -> min_p -> typical_p -> epsilon_cutoff -> eta_cutoff -> draw in
+    one launch (afk_decode_sample_filtered; the contract is in include/afk.h; min_p <= 0, typical_p >= 1, epsilon_cutoff / eta_cutoff outside (0, 1): off).  u [B] fp32 on the device supplies the uniforms; without it they come from Philox4x32-10 keyed by the 64-bit `seed`, counter
     (*step_base + step_off, row).  probs_out [B, V] fp32 / kept_out [B] int32: the distribution drawn from and the size of its support.  state (int32
     [start, end, slot, position], B == 1) with emb / x_out (and tokens_out / tok_off): the step bookkeeping of afk_decode_select_greedy in the same launch."""
     _chk(logits, torch.float32, "decode_sample logits")
@@ -750,7 +750,8 @@ def decode_sample(logits, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, u=None
         if x_out.numel() < H or not x_out.is_contiguous() or V > emb.shape[0]:
             raise AfkError(f"decode_sample: x_out holds {x_out.numel()} elements, emb is {tuple(emb.shape)} for V = {V}")
     seed = int(seed) & (2 ** 64 - 1)
-    _lib.call("afk_decode_sample", logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0), float(top_p), _p(u),
+    _lib.call("afk_decode_sample_filtered", logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0), float(top_p), float(min_p),
+              float(typical_p), float(epsilon_cutoff), float(eta_cutoff), _p(u),
               seed - 2 ** 64 if seed >= 2 ** 63 else seed, _p(step_base), int(step_off), out.data_ptr(), _p(probs_out),
               probs_out.stride(0) if probs_out is not None else 0, _p(kept_out), _p(tokens_out), int(tok_off), _p(state), _p(emb),
               emb.stride(0) if emb is not None else 0, H, _p(x_out), _stream())

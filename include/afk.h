@@ -395,6 +395,26 @@ int afk_decode_select_greedy(const float* part_val, const int* part_idx, int npa
 int afk_decode_sample(const float* logits, int64_t ld_logits, int B, int V, float temperature, int top_k, float top_p, const float* u, int64_t seed,
                       const int* step_base, int step_off, int64_t* next_token, float* probs_out, int64_t ld_probs, int* kept_out, int64_t* tokens_out, int tok_off,
                       int* state, const void* emb, int64_t ld_emb, int H, void* x_out, void* stream);
+/* afk_decode_sample with the remaining sampling warpers of GenerationMixin._get_logits_processor (transformers/generation/utils.py:1311-1343) - MinPLogitsWarper,
+ * TypicalLogitsWarper, EpsilonLogitsWarper, EtaLogitsWarper (transformers/generation/logits_process.py) - in its order, between steps 3 and 4 of that contract, same
+ * launch.  Every filter's softmax is taken over the set S that the filters in front of it left (the warpers see -inf for a removed token):
+ *   3a. min_p > 0: keeps i in S iff softmax_S(z)_i >= min_p x max softmax_S, i.e. exp(z_i - zmax) >= min_p; evaluated as the floor z_i >= zmax + log(min_p) in z.
+ *       The row maximum is in S here and stays; min_p == 1 keeps exactly the ties with it.
+ *   3b. typical_p < 1: over S, r = softmax_S(z), H = -sum r log r, d_i = |-log r_i - H| = |(zmax - z_i) - sum_S r_j (zmax - z_j)| (log Z cancels).  With the tokens
+ *       taken by ascending d, d* = the d of the first one whose inclusive cumulative r reaches typical_p; keeps every i with d_i <= d* (the warper's
+ *       `(cumulative_probs < mass).sum()` index with its `>` removal: ties in d all stay, the token nearest the entropy always stays).  The kept set is a band in z
+ *       and may exclude the row maximum.
+ *   3c. 0 < epsilon_cutoff < 1: keeps i in S iff softmax_S(z)_i >= epsilon_cutoff; the class of the largest z in S always stays.
+ *   3d. 0 < eta_cutoff < 1: the same rule with the floor eta = min(eta_cutoff, sqrt(eta_cutoff) x exp(-H_S)), H_S the entropy of softmax_S.
+ * Steps 4 - 6 follow on the set that is left; a row with a +inf or with no finite logit answers as step 6 says, whatever the filters.  The set's mass and entropy
+ * term are integer sums of round(exp(z - max) * 2^40) and round(exp(z - max) * (max - z) * 2^40): the token stays a pure function of (logits, parameters, u).
+ * Off: min_p <= 0, typical_p >= 1, epsilon_cutoff / eta_cutoff outside (0, 1); with all four off the launch is afk_decode_sample's, pass for pass and bit for bit.
+ * Refused: min_p > 1, typical_p <= 0, a NaN in any of the four.  Cost in passes over the row: min_p none, typical_p four, epsilon / eta one each
+ * (profiles/decode_sampling_warpers.md). */
+int afk_decode_sample_filtered(const float* logits, int64_t ld_logits, int B, int V, float temperature, int top_k, float top_p, float min_p, float typical_p,
+                               float epsilon_cutoff, float eta_cutoff, const float* u, int64_t seed, const int* step_base, int step_off, int64_t* next_token,
+                               float* probs_out, int64_t ld_probs, int* kept_out, int64_t* tokens_out, int tok_off, int* state, const void* emb, int64_t ld_emb,
+                               int H, void* x_out, void* stream);
 /* Logits processors on the device (csrc/decode_process.hip), one launch for B rows of fp32 logits [B][V] (row stride ld_logits >= V; any V >= 1, any B >= 1),
  * processed IN PLACE: the processors GenerationMixin._get_logits_processor (transformers/generation/utils.py:1174-1290) puts in front of the warpers, in its order -
  * RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor, MinNewTokensLengthLogitsProcessor, SuppressTokensLogitsProcessor,
