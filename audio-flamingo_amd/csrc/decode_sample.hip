@@ -36,6 +36,7 @@ struct SampleArgs {
     long long* next_token; float* probs; int64_t ld_probs; int* kept; long long* tokens_out; int tok_off; int* state; const bf16* emb; int64_t ld_emb; int H;
     bf16* x_out;
     float min_p, typical_p, eps, eta;   // as passed; off: min_p <= 0, typical_p >= 1, eps / eta outside (0, 1)
+    float* scores; int64_t scores_ss, ld_scores; int n_steps;   // afk_decode_sample_scored: the warped row of token t goes to slot t of [n_steps][B][V] (null: not wanted)
 };
 struct Sel { int bin; u64 excl, total, target; };
 
@@ -430,6 +431,19 @@ __global__ __launch_bounds__(NT) void decode_sample_kernel(SampleArgs a) {
             pr[i] = r;
         });
     }
+    if (a.scores && s_step >= 0 && s_step < a.n_steps) {   // what the warper chain leaves in next_token_scores: z on the kept set, -inf elsewhere; s_step was read before the bookkeeping below
+        float* sc = a.scores + (int64_t)s_step * a.scores_ss + (int64_t)b * a.ld_scores;
+        for_each_logit(row, V, t, [&](int i, float x) {
+            float r = -INFINITY;
+            if (mode == 0) {
+                const float z = zval(x, T, div);
+                if (in_set<TYP>(z, thr, zmax, E, dthr)) r = z;
+            } else if (mode == 1) {
+                if (i == tok) r = zval(x, T, div);   // the +inf that wins; mode 2: no id has a positive probability
+            }
+            sc[i] = r;
+        });
+    }
     if (t == 0) {
         a.next_token[b] = tok;
         if (a.kept) a.kept[b] = kept_n;
@@ -450,13 +464,16 @@ __global__ __launch_bounds__(NT) void decode_sample_kernel(SampleArgs a) {
 
 #define ST ((hipStream_t)stream)
 
-extern "C" int afk_decode_sample_filtered(const float* logits, int64_t ld_logits, int B, int V, float temperature, int top_k, float top_p, float min_p, float typical_p,
-                                          float epsilon_cutoff, float eta_cutoff, const float* u, int64_t seed, const int* step_base, int step_off,
-                                          int64_t* next_token, float* probs_out, int64_t ld_probs, int* kept_out, int64_t* tokens_out, int tok_off, int* state,
-                                          const void* emb, int64_t ld_emb, int H, void* x_out, void* stream) {
+extern "C" int afk_decode_sample_scored(const float* logits, int64_t ld_logits, int B, int V, float temperature, int top_k, float top_p, float min_p, float typical_p,
+                                        float epsilon_cutoff, float eta_cutoff, const float* u, int64_t seed, const int* step_base, int step_off,
+                                        int64_t* next_token, float* probs_out, int64_t ld_probs, int* kept_out, int64_t* tokens_out, int tok_off, int* state,
+                                        const void* emb, int64_t ld_emb, int H, void* x_out, float* scores_out, int64_t scores_step_stride, int64_t ld_scores,
+                                        int n_steps, void* stream) {
     AFK_REQUIRE(logits && next_token, "afk_decode_sample: null pointer (logits, next_token)");
     AFK_REQUIRE(B >= 1 && V >= 1 && V <= AFK_SAMPLE_MAX_V && ld_logits >= V && (!probs_out || ld_probs >= V),
                 "afk_decode_sample: unsupported shape (B >= 1, 1 <= V <= %d, row strides >= V)", AFK_SAMPLE_MAX_V);
+    AFK_REQUIRE(!scores_out || (n_steps >= 1 && ld_scores >= V && scores_step_stride >= (int64_t)(B - 1) * ld_scores + V),
+                "afk_decode_sample: scores_out needs n_steps >= 1, ld_scores >= V and scores_step_stride >= (B - 1) * ld_scores + V");
     AFK_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "afk_decode_sample: temperature %g (finite, temperature > 0)", (double)temperature);
     AFK_REQUIRE(top_p > 0.f, "afk_decode_sample: top_p %g (top_p > 0; top_p >= 1 switches the filter off)", (double)top_p);
     AFK_REQUIRE(min_p <= 1.f, "afk_decode_sample: min_p %g (min_p <= 1; min_p <= 0 switches the filter off)", (double)min_p);
@@ -469,7 +486,7 @@ extern "C" int afk_decode_sample_filtered(const float* logits, int64_t ld_logits
     AFK_REQUIRE(state || !tokens_out, "afk_decode_sample: tokens_out is indexed by state[2]: null pointer (state)");
     SampleArgs a = {logits, ld_logits, V, temperature, top_k, top_p, u, (uint32_t)((uint64_t)seed & 0xffffffffu), (uint32_t)((uint64_t)seed >> 32), step_base, step_off,
                     (long long*)next_token, probs_out, ld_probs, kept_out, (long long*)tokens_out, tok_off, state, (const bf16*)emb, ld_emb, H, (bf16*)x_out,
-                    min_p, typical_p, epsilon_cutoff, eta_cutoff};
+                    min_p, typical_p, epsilon_cutoff, eta_cutoff, scores_out, scores_step_stride, ld_scores, scores_out ? n_steps : 0};
     const bool floors = min_p > 0.f || (epsilon_cutoff > 0.f && epsilon_cutoff < 1.f) || (eta_cutoff > 0.f && eta_cutoff < 1.f);
     if (typical_p < 1.f) {
         hipLaunchKernelGGL((decode_sample_kernel<true, true>), dim3(B), dim3(NT), 0, ST, a);
@@ -480,6 +497,14 @@ extern "C" int afk_decode_sample_filtered(const float* logits, int64_t ld_logits
     }
     AFK_LAUNCH_CHECK("afk_decode_sample");
     return AFK_OK;
+}
+
+extern "C" int afk_decode_sample_filtered(const float* logits, int64_t ld_logits, int B, int V, float temperature, int top_k, float top_p, float min_p, float typical_p,
+                                          float epsilon_cutoff, float eta_cutoff, const float* u, int64_t seed, const int* step_base, int step_off,
+                                          int64_t* next_token, float* probs_out, int64_t ld_probs, int* kept_out, int64_t* tokens_out, int tok_off, int* state,
+                                          const void* emb, int64_t ld_emb, int H, void* x_out, void* stream) {
+    return afk_decode_sample_scored(logits, ld_logits, B, V, temperature, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, u, seed, step_base, step_off,
+                                    next_token, probs_out, ld_probs, kept_out, tokens_out, tok_off, state, emb, ld_emb, H, x_out, nullptr, 0, 0, 0, stream);
 }
 
 extern "C" int afk_decode_sample(const float* logits, int64_t ld_logits, int B, int V, float temperature, int top_k, float top_p, const float* u, int64_t seed,

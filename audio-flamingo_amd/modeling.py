@@ -26,7 +26,9 @@ Deviations from the oracle surface (documented, not silent):
     filtered and drawn on the device by one launch, ``afk_decode_sample_filtered``, inside the
     replayed step: the ids are a function of the seed, not of torch's generator stream; top-p keeps a class of equal logits whole), or ``num_beams > 1`` (beam search with the
     reference's scoring); ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens`` / ``suppress_tokens`` / ``begin_suppress_tokens`` are applied
-    on the device inside the replayed step (``afk_decode_process``, decode_process.py); ``generation_config`` supplies defaults; constrained / assisted decoding are not built;
+    on the device inside the replayed step (``afk_decode_process``, decode_process.py); ``generation_config`` supplies defaults;
+    ``return_dict_in_generate`` with ``output_scores`` / ``output_logits`` returns an ``AfkGenerateOutput`` (generation_output.py) whose per-step rows are kept from
+    inside the replayed step, and ``compute_transition_scores`` scores it; constrained / assisted decoding are not built;
   * ``attention_mask`` rows must be one contiguous run of ones (left padding - the reference processor's default -, right padding, or
     both); masks with holes raise.  Hidden states of padded positions are zeros-attended garbage in both implementations and are
     never compared.
@@ -1030,18 +1032,27 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             g = greedy
             _lib.call("afk_decode_chain_lm_head", x.data_ptr(), a[lm + "norm.weight"].data.data_ptr(), eps, head.data_ptr(), head.stride(0), head.shape[0], H,
                       g["logits"].data_ptr(), None, None, st)
+            rec = g.get("rec")
+            self._record_rows(rec, "logits", g["logits"], step_base=g["cur"], step_off=g["tok_off"])   # the raw row, in front of the processors
             if g.get("proc"):
                 sel = {} if g.get("sampling") else dict(select=True, tokens_out=g["tok_buf"], tok_off=g["tok_off"], state=g["state"], emb=g["emb"], x_out=g["x0"])
                 _process.apply(g["proc"], g["logits"], next_token=g["nxt"], step_base=g["cur"], step_off=g["tok_off"], **sel)
                 if sel:
+                    # the selecting launch has advanced state[2] (= cur) itself, and the processed row it selected from is still in place: recorded BEHIND it,
+                    # one step further back (rather than inside the launch, which would put a vocabulary-sized store into afk_decode_process for this case only)
+                    self._record_rows(rec, "scores", g["logits"], step_base=g["cur"], step_off=g["tok_off"] - 1)
                     return None
             self._sample_token(g["logits"], g["sampling"], step_base=g["cur"], step_off=g["tok_off"], out=g["nxt"], tokens_out=g["tok_buf"], tok_off=g["tok_off"],
-                               state=g["state"], emb=g["emb"], x_out=g["x0"])
+                               state=g["state"], emb=g["emb"], x_out=g["x0"], **self._scores_kw(rec))
             return None
         if greedy is not None:   # generate()'s state dict: the lm_head launch leaves (max, argmax) per eight rows, the select launch does everything up to the next step
             g = greedy
+            rec = g.get("rec")   # flags off: no logits row is written, as before; on: the same launch also leaves the row (the partial argmax pairs, hence the ids, are the same)
             _lib.call("afk_decode_chain_lm_head", x.data_ptr(), a[lm + "norm.weight"].data.data_ptr(), eps, head.data_ptr(), head.stride(0), head.shape[0], H,
-                      None, g["part_val"].data_ptr(), g["part_idx"].data_ptr(), st)
+                      g["logits"].data_ptr() if rec else None, g["part_val"].data_ptr(), g["part_idx"].data_ptr(), st)
+            if rec:   # no processor: scores and logits are the same rows (one buffer when both are asked for); in front of the select launch, which advances cur
+                self._record_rows(rec, "logits", g["logits"], step_base=g["cur"], step_off=g["tok_off"])
+                self._record_rows(rec, "scores", g["logits"], step_base=g["cur"], step_off=g["tok_off"])
             _lib.call("afk_decode_select_greedy", g["part_val"].data_ptr(), g["part_idx"].data_ptr(), g["part_val"].numel(), g["nxt"].data_ptr(),
                       g["tok_buf"].data_ptr(), g["tok_off"], g["state"].data_ptr(), g["emb"].data_ptr(), g["emb"].stride(0), H, g["x0"].data_ptr(), st)
             return None
@@ -1200,11 +1211,14 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             self._decode_layers_chain(st["x0"], st["cache"], st["pos1"], st["kr1"], st["cur"], aws=st["aws"], head=st["head"], greedy=st)
             return
         logits = self._decode_logits(st)
+        rec = st.get("rec")
+        self._record_rows(rec, "logits", logits, step_base=st["cur"], step_off=st["tok_off"])
         if st.get("proc"):   # the token being generated is number cur + 1 - S0: the processors' (and the draw's) counter lives on the device and advances with the step
             _process.apply(st["proc"], logits, next_token=st["nxt"], step_base=st["cur"], step_off=st["tok_off"])
         if st.get("sampling"):
-            self._sample_token(logits, st["sampling"], step_base=st["cur"], step_off=st["tok_off"], out=st["nxt"])
+            self._sample_token(logits, st["sampling"], step_base=st["cur"], step_off=st["tok_off"], out=st["nxt"], **self._scores_kw(rec))
         else:
+            self._record_rows(rec, "scores", logits, step_base=st["cur"], step_off=st["tok_off"])
             st["nxt"].copy_(self._select_token(logits))
         (st["advance"] if "advance" in st else st["cur"]).add_(1)   # single sequence: cur, position and the key-range end live in one tensor (generate())
 
@@ -1330,6 +1344,22 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         return torch.multinomial(logits.softmax(-1), 1, generator=gen).squeeze(-1)
 
     @staticmethod
+    def _record_rows(rec, which, rows, *, step_base=None, step_off=0):
+        """generate(output_logits / output_scores): one afk_decode_record launch that keeps the fp32 rows [B, V] in slot *step_base + step_off of rec[which]
+        ([max_new_tokens, B, V]).  Nothing is enqueued when the buffer was not asked for, or when `scores` shares the buffer of `logits` (greedy decoding with
+        no processor: the row is recorded once, under "logits")."""
+        if not rec or rec.get(which) is None or (which == "scores" and rec.get("logits") is rec["scores"]):
+            return
+        if rows.dtype != torch.float32 or rows.stride(-1) != 1:   # only what a user logits_processor returned (token 0 and the eager hook loop): the captured
+            rows = rows.float().contiguous()                      # steps hand over the fp32 rows the lm_head wrote, so nothing is allocated or copied there
+        ops.decode_record(rows, rec[which], step_base=step_base, step_off=step_off)
+
+    @staticmethod
+    def _scores_kw(rec):
+        """the sampler's keywords that make its launch keep the warped row (afk_decode_sample_scored); {} when scores were not asked for"""
+        return dict(scores_out=rec["scores"]) if rec and rec.get("scores") is not None else {}
+
+    @staticmethod
     def _sample_token(logits, sampling, **kw):
         """the sampling chain of _select_token on the device, in one launch and with no host state (ops.decode_sample): temperature -> top-k -> top-p ->
         min_p -> typical_p -> epsilon_cutoff -> eta_cutoff -> the draw from a counter-based generator keyed by sampling["seed"]; kw: the draw's counter
@@ -1365,7 +1395,24 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         replays in the decode graph.  Gating and validation are the reference's (decode_process.resolve_warpers): min_p outside [0, 1] and typical_p <= 0 raise
         ValueError, typical_p >= 1 and epsilon_cutoff / eta_cutoff outside (0, 1) are inactive, and do_sample=False ignores all four.  Left at their defaults they
         are taken from the generation config like top_p - a config that carries one of them was ignored before and now changes the distribution sampled from, as
-        it does in the reference.  Cache handling as
+        it does in the reference.
+        return_dict_in_generate / output_scores / output_logits (keyword first, else the generation config: GenerationMixin's rule, utils.py:2829-2837):
+        with return_dict_in_generate the call returns an AfkGenerateOutput (generation_output.py: GenerateDecoderOnlyOutput's fields and access surface) -
+        `sequences`, exactly the tensor the same call returns without the flags; `logits` / `scores`, tuples of n = sequences.shape[1] - S0 tensors [B, V] fp32:
+        the raw lm_head rows, and the rows after the built-in processors, any user logits_processor and - sampled - the warpers (logits / temperature on the
+        kept set, -inf elsewhere); `past_key_values`, the AfkKVCache of every token but the last, which forward(past_key_values=...) takes as is.  The rows are
+        kept from inside the captured step - one afk_decode_record launch per kind and step, none for sampled scores, which the sampler's launch writes itself
+        (afk_decode_sample_scored) - into ONE buffer per kind allocated up front: max_new_tokens x B x V x 4 bytes each, 608 KB per row and step at the AF3
+        vocabulary (a 256-token, 8-row call with both kinds holds 2.5 GB); the tuples are views of it.  Greedy decoding with no processor returns the same
+        views under both names (the reference returns the same tensors).  output_scores / output_logits without return_dict_in_generate collect nothing and
+        return the plain tensor, silently, as the reference does.  A generation config that sets return_dict_in_generate=True was ignored before and now
+        returns the object - and raises where it also asks for one of the refused combinations below, as a config with output_attentions / output_hidden_states
+        now does.  With the flags off nothing extra is enqueued.  After a row's own EOS this implementation keeps feeding the token it selected
+        where the reference feeds pad_token_id: the entries of `scores` / `logits` of a row at steps behind its first EOS are unspecified.  do_sample=True
+        with top_k=1 stays the greedy shortcut it is (routing it through the sampler could move ids on tied bf16 logits): its `scores` are the processed,
+        un-warped rows.  Refused, by an AfkError that names the combination: the output object with num_beams > 1 (the reference returns another class, with
+        beam_indices), with use_cache=False or with AFK_EXACT_FP32=1; output_attentions / output_hidden_states.  compute_transition_scores() scores the result.
+        Cache handling as
         Qwen2Attention.forward modeling_qwen2.py:213-214).  Prefill runs the prompt once and fills a per-layer KV cache; every new
         token then costs one pass over the weights and one Q=1 attention over the cache.  Batches may be LEFT padded
         (attention_mask, as the processor pads): positions count real tokens only and padded keys are never visible.
@@ -1373,7 +1420,8 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         replayed (use_graph=None: whenever more than 3 tokens are requested)."""
         self._require_hip()
         procs, criteria, streamer = kwargs.pop("logits_processor", None), kwargs.pop("stopping_criteria", None), kwargs.pop("streamer", None)
-        for k in ("return_dict_in_generate", "output_scores", "output_logits", "synced_gpus", "use_model_defaults", "tokenizer", "assistant_model"):
+        out_kw = {k: kwargs.pop(k, None) for k in ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")}
+        for k in ("synced_gpus", "use_model_defaults", "tokenizer", "assistant_model"):
             if kwargs.get(k):
                 raise AfkError(f"generate({k}=...) is not supported by this implementation")
             kwargs.pop(k, None)
@@ -1390,7 +1438,9 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         spec = _process.resolve(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, begin_suppress_tokens, eos_token_id=eos_token_id,
                                 generation_config=gc)   # the five logits processors: keyword, else generation config, validated as the reference does
         from . import exact as _exact
+        from . import generation_output as _gout
 
+        flags = _gout.resolve_output_flags(**out_kw, generation_config=gc, num_beams=int(num_beams), use_cache=bool(use_cache), exact_fp32=_exact.ENABLED)
         if int(max_new_tokens) <= 0:   # GenerationMixin refuses it as well (generation/configuration_utils.py validate())
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         if spec.active and (num_beams > 1 or not use_cache):
@@ -1439,15 +1489,24 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         if num_beams > 1:
             return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), int(max_new_tokens), eos_token_id, pad_token_id, float(length_penalty), early_stopping)
         first_logits = ops.gemm_nt(last, self.arena["lm_head.weight"].data).float()
+        rec = None
+        if flags.collect:   # one [max_new_tokens, B, V] fp32 buffer per kind, allocated once: static memory the captured step writes a slot of
+            new_buf = lambda: torch.empty((int(max_new_tokens), B, first_logits.shape[1]), device=dev, dtype=torch.float32)
+            rec = {"logits": new_buf() if flags.logits else None, "scores": None}
+            if flags.scores:   # greedy with no processor of any kind: the reference returns the same tensors in both tuples - one buffer, one record per step
+                rec["scores"] = rec["logits"] if (flags.logits and not sampling and not spec.active and not procs) else new_buf()
+            self._record_rows(rec, "logits", first_logits, step_off=0)   # token 0, eagerly, with the kernel of the captured steps
         proc = None
         if spec.active:   # token 0, eagerly, with the kernel of the captured steps; in front of the user's processors (GenerationMixin._merge_criteria_processor_list)
             proc = _process.build_state(spec, ids, int(max_new_tokens), first_logits.shape[1])
             _process.apply(proc, first_logits)
         if procs:
             first_logits = procs(ids, first_logits)
+        if not sampling:
+            self._record_rows(rec, "scores", first_logits, step_off=0)
         st = {"cache": (Kc, Vt), "lo": lo, "head": self.arena["lm_head.weight"].data, "emb": self.arena[self._lm + "embed_tokens.weight"].data,
-              "cur": torch.full((1,), S0, device=dev, dtype=torch.int32), "sampling": sampling, "tok_off": 1 - S0, "proc": proc,
-              "nxt": self._sample_token(first_logits, sampling) if sampling else self._select_token(first_logits)}   # the first token is draw 0
+              "cur": torch.full((1,), S0, device=dev, dtype=torch.int32), "sampling": sampling, "tok_off": 1 - S0, "proc": proc, "rec": rec,
+              "nxt": self._sample_token(first_logits, sampling, **self._scores_kw(rec)) if sampling else self._select_token(first_logits)}   # the first token is draw 0
         if B == 1:   # one device tensor [lo, key-range end, cache slot, position] -> the views the kernels read; one add per step moves the last three
             state = torch.cat([lo, torch.tensor([S0 + 1, S0], device=dev, dtype=torch.int32), S0 - lo]).contiguous()
             st.update(cur=state[2:3], kr1=state[0:2], pos1=state[3:4], advance=state[1:4], state=state)
@@ -1455,13 +1514,14 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
                 tok_buf = torch.zeros(max_new_tokens, device=dev, dtype=torch.int64)
                 tok_buf[0] = st["nxt"][0]
                 st.update(x0=st["emb"].index_select(0, st["nxt"]).contiguous(), aws=self._decode_attn_workspace(dev, Vt.shape[4]), tok_buf=tok_buf)
-                if sampling or proc:
+                if sampling or proc or rec:
                     st.update(logits=torch.empty((1, st["head"].shape[0]), device=dev, dtype=torch.float32))
-                else:
+                if not (sampling or proc):
                     st.update(part_val=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.float32),
                               part_idx=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.int32))
         if hooks:
-            return self._generate_with_hooks(ids, st, first_logits, int(max_new_tokens), procs, criteria, streamer, eos_token_id, pad_token_id)
+            seq = self._generate_with_hooks(ids, st, first_logits, int(max_new_tokens), procs, criteria, streamer, eos_token_id, pad_token_id)
+            return self._generate_output(flags, seq, S0, rec, st["cache"], lo)
         on_device = "x0" in st
         n_new = 1
         toks = [st["nxt"].clone()]
@@ -1488,7 +1548,42 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         if eos_token_id is not None:  # everything after a row's first EOS becomes padding (GenerationMixin semantics)
             after = (new == eos_token_id).cumsum(1) - (new == eos_token_id).long() > 0
             new = torch.where(after, torch.full_like(new, pad_token_id if pad_token_id is not None else eos_token_id), new)
-        return torch.cat([ids, new], dim=1)
+        return self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st["cache"], lo)
+
+    @staticmethod
+    def _generate_output(flags, sequences, S0, rec, cache, lo):
+        """what generate() returns: the plain sequences, or under return_dict_in_generate the AfkGenerateOutput around them - n = generated columns, scores /
+        logits = the first n slots of the recorded buffers as tuples of [B, V] views, past_key_values = the cache of every token but the last"""
+        if not flags.return_dict:
+            return sequences
+        from .generation_output import AfkGenerateOutput
+
+        n = sequences.shape[1] - S0
+        rows = lambda k: tuple(rec[k][i] for i in range(n)) if rec and rec.get(k) is not None else None
+        logits = rows("logits")
+        scores = logits if (rec and rec.get("scores") is not None and rec["scores"] is rec.get("logits")) else rows("scores")   # the same tensor objects, as the reference
+        return AfkGenerateOutput(sequences=sequences, scores=scores, logits=logits, past_key_values=AfkKVCache(cache[0], cache[1], lo, S0 + n - 1))
+
+    def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits=False):
+        """GenerationMixin.compute_transition_scores (transformers/generation/utils.py:1433-1555) for greedy / sampled outputs: [B, len(scores)] fp32, the
+        score of every generated token (the last len(scores) columns of `sequences`) in `scores` - or `logits` - as generate(return_dict_in_generate=True)
+        returned them; normalize_logits: minus the row's logsumexp, i.e. log-probabilities (-inf entries, the tokens a processor or warper removed, count as
+        probability 0).  One launch (afk_transition_scores); tuples that are consecutive views of one buffer - what generate() returns - are read in place,
+        anything else is stacked first.  beam_indices: beam-search outputs are not produced by this implementation's generate() and are refused."""
+        if beam_indices is not None:
+            raise AfkError("compute_transition_scores(beam_indices=...) is not supported: generate() returns no beam-search outputs")
+        from .generation_output import step_buffer_view
+
+        scores = tuple(scores)
+        if not scores:
+            raise AfkError("compute_transition_scores: `scores` is empty")
+        if sequences.dim() != 2 or sequences.shape[1] < len(scores) or sequences.shape[0] != scores[0].shape[0]:
+            raise AfkError(f"compute_transition_scores: sequences {tuple(sequences.shape)} do not hold {len(scores)} generated columns for {scores[0].shape[0]} rows")
+        buf = step_buffer_view(scores) if scores[0].is_cuda else None
+        if buf is None:
+            buf = torch.stack([s.to(self.device_, torch.float32) for s in scores]).contiguous()
+        tokens = sequences[:, sequences.shape[1] - len(scores):].to(buf.device, torch.int64).contiguous()
+        return ops.transition_scores(buf, tokens, normalize=bool(normalize_logits))
 
     @torch.no_grad()
     def _generate_with_hooks(self, ids, st, logits, max_new, procs, criteria, streamer, eos_token_id, pad_token_id):
@@ -1509,11 +1604,17 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             if t > 0:
                 logits = self._decode_logits(st)        # appends the K / V of st["nxt"] at the cache slot st["cur"]
                 (st["advance"] if "advance" in st else st["cur"]).add_(1)
+                self._record_rows(st.get("rec"), "logits", logits, step_off=t)
                 if st.get("proc"):   # the built-in processors first: st["nxt"] is token t - 1 as appended to seq (pad for a finished row)
                     _process.apply(st["proc"], logits, next_token=st["nxt"], step_off=t)
                 if procs:
                     logits = procs(seq, logits)
-            tok = self._sample_token(logits, st["sampling"], step_off=t) if st.get("sampling") else self._select_token(logits)
+            if st.get("sampling"):   # token 0 is drawn a second time here (generate() drew it for st["nxt"]): the same draw, the same scores row
+                tok = self._sample_token(logits, st["sampling"], step_off=t, **self._scores_kw(st.get("rec")))
+            else:
+                if t > 0:
+                    self._record_rows(st.get("rec"), "scores", logits, step_off=t)
+                tok = self._select_token(logits)
             tok = torch.where(done, torch.full_like(tok, pad), tok)
             seq = torch.cat([seq, tok[:, None]], dim=1)
             if streamer is not None:

@@ -720,11 +720,14 @@ def scatter_rows(src, rows, M):
 
 # ---------------------------------------------------------------------------------------------- token sampling
 def decode_sample(logits, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, u=None, step_base=None, step_off=0, out=None, probs_out=None, kept_out=None,
-                  tokens_out=None, tok_off=0, state=None, emb=None, x_out=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+                  tokens_out=None, tok_off=0, state=None, emb=None, x_out=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, scores_out=None,
+                  n_steps=None):
     """next_token [B] (int64) drawn from the fp32 logits [B, V]: temperature -> top-k -> top-p -> min_p -> typical_p -> epsilon_cutoff -> eta_cutoff -> draw in
     one launch (afk_decode_sample_filtered; the contract is in include/afk.h; min_p <= 0, typical_p >= 1, epsilon_cutoff / eta_cutoff outside (0, 1): off).  u [B] fp32 on the device supplies the uniforms; without it they come from Philox4x32-10 keyed by the 64-bit `seed`, counter
     (*step_base + step_off, row).  probs_out [B, V] fp32 / kept_out [B] int32: the distribution drawn from and the size of its support.  state (int32
-    [start, end, slot, position], B == 1) with emb / x_out (and tokens_out / tok_off): the step bookkeeping of afk_decode_select_greedy in the same launch."""
+    [start, end, slot, position], B == 1) with emb / x_out (and tokens_out / tok_off): the step bookkeeping of afk_decode_select_greedy in the same launch.
+    scores_out [n_steps, B, V] fp32 (n_steps: the slots the launch may write, default all of them): slot *step_base + step_off receives the warped row - logits /
+    temperature on the kept set, -inf elsewhere (afk_decode_sample_scored; without scores_out the launch is afk_decode_sample_filtered's)."""
     _chk(logits, torch.float32, "decode_sample logits")
     if logits.dim() != 2 or logits.stride(1) != 1:
         raise AfkError(f"decode_sample logits: [B, V] with unit column stride, got {tuple(logits.shape)} strides {logits.stride()}")
@@ -749,12 +752,70 @@ def decode_sample(logits, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, u=None
         H = emb.shape[1]
         if x_out.numel() < H or not x_out.is_contiguous() or V > emb.shape[0]:
             raise AfkError(f"decode_sample: x_out holds {x_out.numel()} elements, emb is {tuple(emb.shape)} for V = {V}")
+    scored = ()
+    if scores_out is not None:
+        n_steps = _step_buffer_chk(scores_out, B, V, n_steps, "decode_sample scores_out")
+        scored = (scores_out.data_ptr(), scores_out.stride(0), scores_out.stride(1), n_steps)
+    elif n_steps is not None:
+        raise AfkError("decode_sample: n_steps counts the slots of scores_out, which was not given")
     seed = int(seed) & (2 ** 64 - 1)
-    _lib.call("afk_decode_sample_filtered", logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0), float(top_p), float(min_p),
-              float(typical_p), float(epsilon_cutoff), float(eta_cutoff), _p(u),
+    _lib.call("afk_decode_sample_scored" if scored else "afk_decode_sample_filtered", logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0),
+              float(top_p), float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff), _p(u),
               seed - 2 ** 64 if seed >= 2 ** 63 else seed, _p(step_base), int(step_off), out.data_ptr(), _p(probs_out),
               probs_out.stride(0) if probs_out is not None else 0, _p(kept_out), _p(tokens_out), int(tok_off), _p(state), _p(emb),
-              emb.stride(0) if emb is not None else 0, H, _p(x_out), _stream())
+              emb.stride(0) if emb is not None else 0, H, _p(x_out), *scored, _stream())
+    return out
+
+
+def _step_buffer_chk(buf, B, V, n_steps, name):
+    """buf: the [slots, B, V] fp32 buffer a decode step writes one slot of (unit column stride, rows and slots that do not overlap) -> the slot count to pass"""
+    _chk(buf, torch.float32, name)
+    if buf.dim() != 3 or tuple(buf.shape[1:]) != (B, V) or buf.shape[0] < 1 or buf.stride(2) != 1 or buf.stride(1) < V or buf.stride(0) < (B - 1) * buf.stride(1) + V:
+        raise AfkError(f"{name}: [n_steps, {B}, {V}] with unit column stride and non-overlapping rows, got {tuple(buf.shape)} strides {buf.stride()}")
+    n = buf.shape[0] if n_steps is None else int(n_steps)
+    if not 1 <= n <= buf.shape[0]:
+        raise AfkError(f"{name}: n_steps {n} outside the buffer's {buf.shape[0]} slots")
+    return n
+
+
+def decode_record(src, dst, *, step_base=None, step_off=0, n_steps=None):
+    """dst[t] = src, a bit copy of the fp32 rows [B, V] into slot t = *step_base + step_off of dst [n_steps, B, V] in one launch (afk_decode_record; the contract
+    is in include/afk.h): how generate() keeps a step's logits / scores from inside the captured step.  step_base: int32 on the device (None = 0); a t outside
+    [0, n_steps) writes nothing (refused here where the host knows t, i.e. without step_base).  -> dst"""
+    _chk(src, torch.float32, "decode_record src")
+    if src.dim() != 2 or src.stride(1) != 1 or src.stride(0) < src.shape[1]:
+        raise AfkError(f"decode_record src: [B, V] with unit column stride, got {tuple(src.shape)} strides {src.stride()}")
+    B, V = src.shape
+    n_steps = _step_buffer_chk(dst, B, V, n_steps, "decode_record dst")
+    if step_base is not None:
+        _chk(step_base, torch.int32, "decode_record step_base")
+        if step_base.numel() < 1 or not step_base.is_contiguous():
+            raise AfkError(f"decode_record step_base: a contiguous tensor of at least 1 element, got {tuple(step_base.shape)}")
+    elif not 0 <= int(step_off) < n_steps:
+        raise AfkError(f"decode_record: step {int(step_off)} outside the buffer's {n_steps} slots")
+    _lib.call("afk_decode_record", src.data_ptr(), src.stride(0), B, V, dst.data_ptr(), dst.stride(0), dst.stride(1), n_steps, _p(step_base), int(step_off), _stream())
+    return dst
+
+
+def transition_scores(scores, tokens, *, normalize=False, out=None):
+    """out [B, T] fp32 = scores[t, b, tokens[b, t]] - (normalize: logsumexp of that row), scores [T, B, V] fp32 with unit column stride, tokens [B, T] int64
+    (afk_transition_scores: GenerationMixin.compute_transition_scores without beam_indices).  The ids are validated on the host (one sync: a post-hoc call)."""
+    _chk(scores, torch.float32, "transition_scores scores")
+    if scores.dim() != 3 or scores.stride(2) != 1 or scores.stride(1) < scores.shape[2] or scores.shape[0] < 1:
+        raise AfkError(f"transition_scores scores: [T, B, V] with unit column stride, got {tuple(scores.shape)} strides {scores.stride()}")
+    T, B, V = scores.shape
+    _chk(tokens, torch.int64, "transition_scores tokens")
+    if tuple(tokens.shape) != (B, T) or tokens.stride(1) != 1:
+        raise AfkError(f"transition_scores tokens: [{B}, {T}] with unit column stride, got {tuple(tokens.shape)} strides {tokens.stride()}")
+    if bool(((tokens < 0) | (tokens >= V)).any()):
+        raise AfkError(f"transition_scores tokens: ids outside the vocabulary [0, {V})")
+    if out is None:
+        out = torch.empty((B, T), device=scores.device, dtype=torch.float32)
+    _chk(out, torch.float32, "transition_scores out")
+    if tuple(out.shape) != (B, T) or out.stride(1) != 1:
+        raise AfkError(f"transition_scores out: [{B}, {T}] with unit column stride, got {tuple(out.shape)} strides {out.stride()}")
+    _lib.call("afk_transition_scores", scores.data_ptr(), scores.stride(0), scores.stride(1), T, B, V, tokens.data_ptr(), tokens.stride(0), 1 if normalize else 0,
+              out.data_ptr(), out.stride(0), _stream())
     return out
 
 

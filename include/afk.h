@@ -415,6 +415,28 @@ int afk_decode_sample_filtered(const float* logits, int64_t ld_logits, int B, in
                                float epsilon_cutoff, float eta_cutoff, const float* u, int64_t seed, const int* step_base, int step_off, int64_t* next_token,
                                float* probs_out, int64_t ld_probs, int* kept_out, int64_t* tokens_out, int tok_off, int* state, const void* emb, int64_t ld_emb,
                                int H, void* x_out, void* stream);
+/* afk_decode_sample_filtered that also keeps the warped row (generate(output_scores=True)): scores_out [n_steps][B][V] fp32 (slot stride scores_step_stride, row stride
+ * ld_scores >= V; null = not wanted, and the launch is afk_decode_sample_filtered's).  Row b of slot t = *step_base + step_off (read before the bookkeeping block
+ * advances the state it may live in) receives what the reference's warper chain leaves in next_token_scores: z_i = logits_i / temperature (the fp32 division of step 1,
+ * the row untouched at temperature == 1; -0 is stored as +0) for every token of the kept set - exactly the tokens with probs_out > 0 - and -inf for every other one.
+ * A row with a +inf holds it at the id that is answered and -inf elsewhere; a row with no finite logit is all -inf.  t outside [0, n_steps) writes no score (token,
+ * probs_out, kept_out and the bookkeeping are unaffected).  The drawn token does not depend on scores_out. */
+int afk_decode_sample_scored(const float* logits, int64_t ld_logits, int B, int V, float temperature, int top_k, float top_p, float min_p, float typical_p,
+                             float epsilon_cutoff, float eta_cutoff, const float* u, int64_t seed, const int* step_base, int step_off, int64_t* next_token,
+                             float* probs_out, int64_t ld_probs, int* kept_out, int64_t* tokens_out, int tok_off, int* state, const void* emb, int64_t ld_emb,
+                             int H, void* x_out, float* scores_out, int64_t scores_step_stride, int64_t ld_scores, int n_steps, void* stream);
+/* Keeping a step's row from inside the captured decode step (csrc/decode_record.hip; generate(output_logits / output_scores)): dst[t * step_stride + b * ld_dst + i] =
+ * src[b * ld_src + i] for b < B, i < V, copied as 32-bit words (NaN payloads, -0 and the infinities survive), t = *step_base + step_off (step_base: device int32,
+ * null = 0; the convention of afk_decode_sample).  t outside [0, n_steps) writes nothing: a replay past the buffer is harmless.  Any V >= 1 and any 4-byte aligned
+ * rows (16-byte stores behind a scalar head, a scalar tail); grid = B x 16 KB column chunks.  Enqueue-only, no allocation, capturable. */
+int afk_decode_record(const float* src, int64_t ld_src, int B, int V, float* dst, int64_t step_stride, int64_t ld_dst, int n_steps, const int* step_base,
+                      int step_off, void* stream);
+/* GenerationMixin.compute_transition_scores without beam_indices (transformers/generation/utils.py:1433-1555) on scores [T][B][V] fp32 (slot stride step_stride, row
+ * stride ld): out[b * ld_out + t] = scores[t][b][tok] - (normalize ? logsumexp_i scores[t][b][i] : 0), tok = tokens[b * ld_tokens + t] (the caller guarantees
+ * 0 <= tok < V; an id outside answers NaN and reads nothing).  One 1024-thread block per (t, b); the maximum first, then the fp32 sum of expf(x - max) in one fixed
+ * order whatever the shape.  -inf entries contribute 0; a row with no finite entry answers NaN under normalize, as log_softmax does. */
+int afk_transition_scores(const float* scores, int64_t step_stride, int64_t ld, int T, int B, int V, const int64_t* tokens, int64_t ld_tokens, int normalize,
+                          float* out, int64_t ld_out, void* stream);
 /* Logits processors on the device (csrc/decode_process.hip), one launch for B rows of fp32 logits [B][V] (row stride ld_logits >= V; any V >= 1, any B >= 1),
  * processed IN PLACE: the processors GenerationMixin._get_logits_processor (transformers/generation/utils.py:1174-1290) puts in front of the warpers, in its order -
  * RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor, MinNewTokensLengthLogitsProcessor, SuppressTokensLogitsProcessor,
