@@ -28,7 +28,8 @@ Deviations from the oracle surface (documented, not silent):
     reference's scoring); ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens`` / ``suppress_tokens`` / ``begin_suppress_tokens`` are applied
     on the device inside the replayed step (``afk_decode_process``, decode_process.py); ``generation_config`` supplies defaults;
     ``return_dict_in_generate`` with ``output_scores`` / ``output_logits`` returns an ``AfkGenerateOutput`` (generation_output.py) whose per-step rows are kept from
-    inside the replayed step, and ``compute_transition_scores`` scores it; constrained / assisted decoding are not built;
+    inside the replayed step, and ``compute_transition_scores`` scores it; ``eos_token_id`` as a list and ``stop_strings=`` / ``tokenizer=`` are decided by
+    one launch inside the replayed step (``afk_decode_stop``, decode_stop.py); constrained / assisted decoding are not built;
   * ``attention_mask`` rows must be one contiguous run of ones (left padding - the reference processor's default -, right padding, or
     both); masks with holes raise.  Hidden states of padded positions are zeros-attended garbage in both implementations and are
     never compared.
@@ -44,6 +45,7 @@ from torch import nn
 
 from . import _lib, ops
 from . import decode_process as _process
+from . import decode_stop as _stop
 from ._lib import AfkError
 from .arena import Arena
 from . import functional as F_
@@ -1209,6 +1211,8 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         """one greedy or sampled decode step on static buffers (everything position-dependent lives on the device): HIP-graph capturable"""
         if "x0" in st:   # one sequence: 5 launches per layer + lm_head + ONE launch for argmax or the draw / token / positions / the next embedding row
             self._decode_layers_chain(st["x0"], st["cache"], st["pos1"], st["kr1"], st["cur"], aws=st["aws"], head=st["head"], greedy=st)
+            if st.get("stop"):   # behind the selection launch, which has advanced cur (= state[2]) already: one step back.  The next embedding row is in x0: no pad is fed
+                _stop.apply(st["stop"], st["nxt"], step_base=st["cur"], step_off=st["tok_off"] - 1)
             return
         logits = self._decode_logits(st)
         rec = st.get("rec")
@@ -1220,6 +1224,8 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         else:
             self._record_rows(rec, "scores", logits, step_base=st["cur"], step_off=st["tok_off"])
             st["nxt"].copy_(self._select_token(logits))
+        if st.get("stop"):   # the stopping rule on the token just selected; a row that finished earlier emits pad_token_id and the next step embeds it
+            _stop.apply(st["stop"], st["nxt"], step_base=st["cur"], step_off=st["tok_off"], feed_pad=True)
         (st["advance"] if "advance" in st else st["cur"]).add_(1)   # single sequence: cur, position and the key-range end live in one tensor (generate())
 
     @torch.no_grad()
@@ -1407,11 +1413,25 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         views under both names (the reference returns the same tensors).  output_scores / output_logits without return_dict_in_generate collect nothing and
         return the plain tensor, silently, as the reference does.  A generation config that sets return_dict_in_generate=True was ignored before and now
         returns the object - and raises where it also asks for one of the refused combinations below, as a config with output_attentions / output_hidden_states
-        now does.  With the flags off nothing extra is enqueued.  After a row's own EOS this implementation keeps feeding the token it selected
-        where the reference feeds pad_token_id: the entries of `scores` / `logits` of a row at steps behind its first EOS are unspecified.  do_sample=True
+        now does.  With the flags off nothing extra is enqueued.  do_sample=True
         with top_k=1 stays the greedy shortcut it is (routing it through the sampler could move ids on tied bf16 logits): its `scores` are the processed,
         un-warped rows.  Refused, by an AfkError that names the combination: the output object with num_beams > 1 (the reference returns another class, with
         beam_indices), with use_cache=False or with AFK_EXACT_FP32=1; output_attentions / output_hidden_states.  compute_transition_scores() scores the result.
+        Stopping.  eos_token_id: an int, list, tuple or tensor (keyword, else the generation config - Qwen2.5 ships [151645, 151643]); pad_token_id defaults to
+        the first eos id; stop_strings= (a string or a list; keyword, else the generation config) needs tokenizer= and raises the reference's ValueError without
+        one (decode_stop.resolve).  With MORE THAN ONE eos id, or with stop strings, the rule is ONE launch of the step (afk_decode_stop; decode_stop.py): it
+        appends the token just selected to a device-resident id buffer - the prompt ids as passed, then the emitted tokens -, judges the row (EosTokenCriteria;
+        StopStringCriteria over the table that class computes: it is constructed on the host and its table uploaded once), records the step at which the row
+        finished, and for a row that finished earlier emits pad_token_id and - in the batched step - feeds it to the next step, as the reference does.  Greedy
+        and sampled steps with it still replay in the decode graph; the loop polls a two-word status every 8th step, and the result is cut at the step at which
+        the last row finished: the reference's shape and padding, which `scores`, `logits` and `past_key_values` follow, and the `scores` / `logits` of a
+        batched row behind its stop are the rows the reference computes.  The hook loop (below) runs the same launch eagerly, in front of the user's
+        stopping_criteria.  With a SINGLE eos id and no stop string - a list holding one id included - generate() enqueues exactly what it did before this
+        route existed and returns what it returned: the loop compares token buffers on the host every 8th step, so the length is rounded up to that poll
+        (everything behind a row's first EOS is pad_token_id), and a batched row keeps feeding the token it selected after its own EOS, so there the entries
+        of `scores` / `logits` of a row behind its first EOS are unspecified.  Unifying the two routes is a follow-up.  Refused, by an AfkError that names the
+        combination: stop strings with num_beams > 1, with use_cache=False or with AFK_EXACT_FP32=1; tokenizer= when no stop string is active.  Not covered:
+        max_time, ConfidenceCriteria, user criteria objects inside the graph.
         Cache handling as
         Qwen2Attention.forward modeling_qwen2.py:213-214).  Prefill runs the prompt once and fills a per-layer KV cache; every new
         token then costs one pass over the weights and one Q=1 attention over the cache.  Batches may be LEFT padded
@@ -1421,7 +1441,8 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         self._require_hip()
         procs, criteria, streamer = kwargs.pop("logits_processor", None), kwargs.pop("stopping_criteria", None), kwargs.pop("streamer", None)
         out_kw = {k: kwargs.pop(k, None) for k in ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")}
-        for k in ("synced_gpus", "use_model_defaults", "tokenizer", "assistant_model"):
+        stop_strings, tokenizer = kwargs.pop("stop_strings", None), kwargs.pop("tokenizer", None) or None
+        for k in ("synced_gpus", "use_model_defaults", "assistant_model"):
             if kwargs.get(k):
                 raise AfkError(f"generate({k}=...) is not supported by this implementation")
             kwargs.pop(k, None)
@@ -1439,6 +1460,14 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
                                 generation_config=gc)   # the five logits processors: keyword, else generation config, validated as the reference does
         from . import exact as _exact
         from . import generation_output as _gout
+
+        # the stopping rule: the eos ids as a tuple, pad defaulted to the first of them, stop strings (keyword, else generation config) with their refusals
+        stop_spec = _stop.resolve(eos_token_id, pad_token_id, stop_strings, tokenizer, generation_config=gc, num_beams=int(num_beams), use_cache=bool(use_cache),
+                                  exact_fp32=_exact.ENABLED)
+        if len(stop_spec.eos) == 1:
+            eos_token_id = stop_spec.eos[0]         # a list holding one id is the scalar case
+        elif stop_spec.eos:
+            eos_token_id = list(stop_spec.eos)      # beam search, the exact path and the hook loop take lists; the graph / eager loop takes the device route
 
         flags = _gout.resolve_output_flags(**out_kw, generation_config=gc, num_beams=int(num_beams), use_cache=bool(use_cache), exact_fp32=_exact.ENABLED)
         if int(max_new_tokens) <= 0:   # GenerationMixin refuses it as well (generation/configuration_utils.py validate())
@@ -1507,6 +1536,11 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         st = {"cache": (Kc, Vt), "lo": lo, "head": self.arena["lm_head.weight"].data, "emb": self.arena[self._lm + "embed_tokens.weight"].data,
               "cur": torch.full((1,), S0, device=dev, dtype=torch.int32), "sampling": sampling, "tok_off": 1 - S0, "proc": proc, "rec": rec,
               "nxt": self._sample_token(first_logits, sampling, **self._scores_kw(rec)) if sampling else self._select_token(first_logits)}   # the first token is draw 0
+        stop = None
+        if stop_spec.device:   # more than one eos id, or stop strings: the rule is a launch of the step.  Token 0, eagerly, with the kernel of the captured steps
+            stop = _stop.build_state(stop_spec, ids, int(max_new_tokens), _stop.build_table(tokenizer, stop_spec.stop_strings) if stop_spec.stop_strings else None)
+            _stop.apply(stop, st["nxt"], step_off=0)
+        st["stop"] = stop
         if B == 1:   # one device tensor [lo, key-range end, cache slot, position] -> the views the kernels read; one add per step moves the last three
             state = torch.cat([lo, torch.tensor([S0 + 1, S0], device=dev, dtype=torch.int32), S0 - lo]).contiguous()
             st.update(cur=state[2:3], kr1=state[0:2], pos1=state[3:4], advance=state[1:4], state=state)
@@ -1520,7 +1554,7 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
                     st.update(part_val=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.float32),
                               part_idx=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.int32))
         if hooks:
-            seq = self._generate_with_hooks(ids, st, first_logits, int(max_new_tokens), procs, criteria, streamer, eos_token_id, pad_token_id)
+            seq = self._generate_with_hooks(ids, st, first_logits, int(max_new_tokens), procs, criteria, streamer, eos_token_id, stop_spec.pad)
             return self._generate_output(flags, seq, S0, rec, st["cache"], lo)
         on_device = "x0" in st
         n_new = 1
@@ -1529,7 +1563,10 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             use_graph = max_new_tokens > 3
         graph = None
         for t in range(1, max_new_tokens):
-            if eos_token_id is not None and t % 8 == 0 and bool(((st["tok_buf"][None, :t] if on_device else torch.stack(toks, 1)) == eos_token_id).any(1).all()):
+            if stop is not None:
+                if t % 8 == 0 and stop["status"].tolist()[1] == 0:   # the poll keeps its cadence: one small copy, {last step, rows still open}
+                    break
+            elif eos_token_id is not None and t % 8 == 0 and bool(((st["tok_buf"][None, :t] if on_device else torch.stack(toks, 1)) == eos_token_id).any(1).all()):
                 break
             if use_graph and t == 2:  # step 1 ran eagerly (lazy one-time initialisation inside the library happens outside the capture)
                 torch.cuda.synchronize()
@@ -1544,6 +1581,10 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             if not on_device:
                 toks.append(st["nxt"].clone())
             n_new = t + 1
+        if stop is not None:   # the reference's shape and padding: up to the step at which the last row finished; later steps only touched slots beyond it
+            n_new = min(n_new, min(int(stop["stop_at"].max()), int(max_new_tokens)) + 1)
+            new = stop["ids"][:, S0:S0 + n_new].to(torch.int64)
+            return self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st["cache"], lo)
         new = st["tok_buf"][None, :n_new].clone() if on_device else torch.stack(toks, 1)
         if eos_token_id is not None:  # everything after a row's first EOS becomes padding (GenerationMixin semantics)
             after = (new == eos_token_id).cumsum(1) - (new == eos_token_id).long() > 0
@@ -1597,6 +1638,7 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         eos = None if eos_token_id is None else torch.as_tensor(eos_token_id, device=dev).reshape(-1)
         pad = pad_token_id if pad_token_id is not None else (int(eos[0]) if eos is not None else 0)
         done = torch.zeros(B, device=dev, dtype=torch.bool)
+        stop = st.get("stop")
         seq = ids
         if streamer is not None:
             streamer.put(ids.cpu())
@@ -1616,10 +1658,15 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
                     self._record_rows(st.get("rec"), "scores", logits, step_off=t)
                 tok = self._select_token(logits)
             tok = torch.where(done, torch.full_like(tok, pad), tok)
+            if stop is not None:   # the device rule (eos list, stop strings), eagerly and in front of the user's criteria; token 0 was judged by generate() - the same answer
+                tok = tok.contiguous()
+                _stop.apply(stop, tok, step_off=t, feed_pad=True)
             seq = torch.cat([seq, tok[:, None]], dim=1)
             if streamer is not None:
                 streamer.put(tok.cpu())
-            if eos is not None:
+            if stop is not None:
+                done = done | (stop["stop_at"] <= t)
+            elif eos is not None:
                 done = done | torch.isin(tok, eos)
             if criteria:
                 r = criteria(seq, logits)
@@ -1641,7 +1688,8 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
                                logits_to_keep=1)
             nxt = out.logits[:, -1, :].float().argmax(-1, keepdim=True)
             ids = torch.cat([ids, nxt], dim=1)
-            if eos_token_id is not None and bool((nxt == eos_token_id).all()):
+            if eos_token_id is not None and bool(torch.isin(nxt, torch.as_tensor(eos_token_id, device=nxt.device)).all() if isinstance(eos_token_id, list)
+                                                 else (nxt == eos_token_id).all()):
                 break
         return ids
 

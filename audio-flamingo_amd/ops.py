@@ -860,6 +860,46 @@ def decode_process(logits, hist, seen, *, S0, penalty=1.0, ngram=0, suppress=Non
     return logits
 
 
+def decode_stop(next_token, ids, stop_at, *, S0, max_new, status=None, step_base=None, step_off=0, eos=None, pad=0, feed_pad=False, table=None, P=0, E=0, S=0,
+                target_lens=None, W=0):
+    """the stopping rule for token t = *step_base + step_off, the one JUST SELECTED into next_token [B] int64, in one launch (afk_decode_stop; the contract is in
+    include/afk.h): a row that finished earlier emits `pad` (and, feed_pad, has it written to next_token); the token joins ids [B, >= S0 + max_new] int32; a row
+    still open is judged - tok in eos (int32 id list on the device), or a stop string matched by StopStringCriteria's rule over its own table [rows, S * (P + E) + 1]
+    int32 with target_lens [S] int32 and W = maximum_token_len - and a hit sets stop_at[b] = t (int32, INT_MAX = open).  status [2] int32 receives
+    {t, rows still open}.  A t outside [0, max_new) writes nothing.  -> stop_at"""
+    _chk(next_token, torch.int64, "decode_stop next_token")
+    if next_token.dim() != 1 or not next_token.is_contiguous():
+        raise AfkError(f"decode_stop next_token: a contiguous [B] tensor, got {tuple(next_token.shape)}")
+    B = next_token.shape[0]
+    _chk(ids, torch.int32, "decode_stop ids")
+    if ids.dim() != 2 or ids.shape[0] != B or ids.stride(1) != 1 or (B > 1 and ids.stride(0) < ids.shape[1]):
+        raise AfkError(f"decode_stop ids: [{B}, >= S0 + max_new] with unit column stride, got {tuple(ids.shape)} strides {ids.stride()}")
+    if int(S0) < 0 or int(max_new) < 1 or int(S0) + int(max_new) > ids.shape[1]:
+        raise AfkError(f"decode_stop: S0 + max_new = {int(S0)} + {int(max_new)} ids in rows of {ids.shape[1]} (S0 >= 0, max_new >= 1, S0 + max_new <= ids.shape[1])")
+    S = int(S)
+    for t_, dt, n, name in ((stop_at, torch.int32, B, "stop_at"), (status, torch.int32, 2, "status"), (step_base, torch.int32, 1, "step_base"),
+                            (eos, torch.int32, 0, "eos"), (target_lens, torch.int32, max(S, 0), "target_lens")):
+        if t_ is not None:
+            _chk(t_, dt, f"decode_stop {name}")
+            if t_.numel() < n or not t_.is_contiguous():
+                raise AfkError(f"decode_stop {name}: a contiguous tensor of at least {n} elements, got {tuple(t_.shape)}")
+    if stop_at is None:
+        raise AfkError("decode_stop: stop_at is needed")
+    rows = vec = 0
+    if S != 0:
+        if table is None or target_lens is None:
+            raise AfkError("decode_stop: stop strings (S > 0) need table and target_lens")
+        _chk(table, torch.int32, "decode_stop table")
+        if table.dim() != 2 or not table.is_contiguous():
+            raise AfkError(f"decode_stop table: a contiguous [rows, vec] tensor, got {tuple(table.shape)} strides {table.stride()}")
+        rows, vec = table.shape
+    n_eos = 0 if eos is None else eos.numel()
+    _lib.call("afk_decode_stop", next_token.data_ptr(), B, ids.data_ptr(), ids.stride(0) if B > 1 else ids.shape[1], int(S0), int(max_new), stop_at.data_ptr(),
+              _p(status), _p(step_base), int(step_off), _p(eos) if n_eos else None, n_eos, int(pad), 1 if feed_pad else 0, _p(table) if S else None, rows, vec,
+              int(P), int(E), S, _p(target_lens) if S else None, int(W), _stream())
+    return stop_at
+
+
 # ---------------------------------------------------------------------------------------------- loss
 def count_valid(labels):
     out = torch.empty(1, device=labels.device, dtype=torch.float32)

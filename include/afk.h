@@ -460,6 +460,26 @@ int afk_decode_process(float* logits, int64_t ld_logits, int B, int V, int* hist
                        const int* step_base, int step_off, int64_t* next_token, float penalty, int no_repeat_ngram_size, const int* suppress, int n_suppress,
                        const int* begin_suppress, int n_begin_suppress, const int* eos, int n_eos, int min_new_tokens, int select, int64_t* tokens_out,
                        int tok_off, int* state, const void* emb, int64_t ld_emb, int H, void* x_out, void* stream);
+/* The stopping rule of the decode step on the device (csrc/decode_stop.hip; generate(eos_token_id=[...], stop_strings=...)): ONE launch per step, a single block
+ * (waves stride over the B rows, the lanes of a wave over the eos ids and the (stop string, end-length) pairs; any B >= 1).  Enqueue-only, no allocation, capturable.
+ * t = *step_base + step_off = the index of the token JUST SELECTED (step_base: device int32, null = 0; the convention of afk_decode_sample); a t outside
+ * [0, max_new) writes nothing.  State, all on the device: next_token [B] int64 (read and written); ids [B][ld_ids] int32 = the S0 prompt ids as passed to generate
+ * (padding and <sound> ids included; the caller fills them once) followed by the emitted tokens; stop_at [B] int32, INT_MAX from the caller = not finished, else the
+ * generated index at which the row finished; status[2] int32 (may be null) = {t, number of rows with stop_at > t}.  Per row b:
+ *   1. tok = next_token[b]; stop_at[b] < t (finished earlier): tok = pad, and with feed_pad != 0 next_token[b] = pad as well, so that the next step embeds the pad id
+ *      (GenerationMixin's next_tokens * unfinished + pad * (1 - unfinished)).
+ *   2. ids[b][S0 + t] = tok.
+ *   3. stop_at[b] >= t: the row's n = S0 + t + 1 ids are judged - EosTokenCriteria: tok is one of eos[n_eos]; StopStringCriteria.__call__
+ *      (transformers/generation/stopping_criteria.py:473-531) over the class's own table: table = embedding_vec [rows][vec] int32, P = max_valid_positions,
+ *      E = max_valid_end_lens, S = num_stop_strings, target_lens[S], W = maximum_token_len, vec == S * (P + E) + 1.  The last min(W, n) ids are taken newest
+ *      first, each clamped to the dummy row rows - 1.  For string s and end lane e: c = table[id_0][P*S + E*s + e]; c <= 0: no match on this lane; else best = c and
+ *      for every older id_j in turn: stop unless c equals one of table[id_j][P*s .. P*s + P), else c += table[id_j][vec - 1], best = max(best, c).  The row matches
+ *      when best >= target_lens[s] for any (s, e).  A hit sets stop_at[b] = t.
+ * Running the same t again on the same next_token reproduces the same state.  S == 0: no stop strings (table may be null).  Refused: null next_token / ids /
+ * stop_at, S0 + max_new > ld_ids, n_eos < 0 (or a count with a null list), S > 0 with a null table / target_lens or vec != S * (P + E) + 1. */
+int afk_decode_stop(int64_t* next_token, int B, int* ids, int64_t ld_ids, int S0, int max_new, int* stop_at, int* status, const int* step_base, int step_off,
+                    const int* eos, int n_eos, int pad, int feed_pad, const int* table, int rows, int vec, int P, int E, int S, const int* target_lens, int W,
+                    void* stream);
 /* The same launches for 2 .. 8 sequences decoded together (one new position each; the weights are still read once per step): M input rows h [M][K] (row stride
  * ldh) that are ALREADY normalised where the Linear follows a norm (Qwen2DecoderLayer :270 / :294, Qwen2Model.norm); pos[M] = position of each sequence's new token,
  * *start_dev = the cache slot all of them write; q_out [M][Hq*D] (row stride ldq); k_bs / vt_bs = batch strides of the K / V^T caches (elements).  Rounding points as above. */
