@@ -99,6 +99,24 @@ def resolve_output_flags(return_dict_in_generate=None, output_scores=None, outpu
     return OutputFlags(True, val["output_scores"], val["output_logits"])
 
 
+def resolve_num_return_sequences(num_return_sequences=None, *, generation_config=None, num_beams=1, do_sample=False) -> int:
+    """num_return_sequences of a generate() call: the keyword when it is given (not None), else the generation config's attribute, else 1, validated as
+    GenerationConfig.validate does (transformers/generation/configuration_utils.py, 2.4) and with its messages: more than one sequence needs sampling or beam
+    search, and beam search returns at most num_beams per row."""
+    n = num_return_sequences if num_return_sequences is not None else (getattr(generation_config, "num_return_sequences", None) if generation_config is not None else None)
+    n = 1 if n is None else n
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1:
+        raise ValueError(f"`num_return_sequences` must be a strictly positive integer, but is {n}.")
+    num_beams = 1 if num_beams is None else int(num_beams)
+    if n > 1:
+        if num_beams == 1:
+            if not do_sample:
+                raise ValueError(f"Greedy methods (do_sample != True) without beam search do not support `num_return_sequences` different than 1 (got {n}).")
+        elif n > num_beams:
+            raise ValueError(f"`num_return_sequences` ({n}) has to be smaller or equal to `num_beams` ({num_beams}).")
+    return n
+
+
 def step_buffer_view(rows):
     """rows: a tuple of [B, V] fp32 tensors.  When they are consecutive views of one buffer (same storage, constant positive stride between them, unit column
     stride) -> that buffer as a [T, B, V] view, without a copy; else None (the caller stacks them)."""

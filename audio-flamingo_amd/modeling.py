@@ -1229,20 +1229,28 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         (st["advance"] if "advance" in st else st["cur"]).add_(1)   # single sequence: cur, position and the key-range end live in one tensor (generate())
 
     @torch.no_grad()
-    def _beam_search(self, ids, last_hidden, cache, lo, nb, max_new, eos_token_id, pad_token_id, length_penalty, early_stopping):
+    def _beam_search(self, ids, last_hidden, cache, lo, nb, max_new, eos_token_id, pad_token_id, length_penalty, early_stopping, *, num_return=1,
+                     use_graph=None):
         """Beam search on the KV cache with GenerationMixin's scoring (transformers/generation/utils.py:3008-3400): every batch row keeps `nb`
         running beams ranked by accumulated log-probability; at each step the best (n_eos + 1) * nb continuations over all beams are drawn, the
         ones among the top nb that end (EOS, or the length limit) compete for the row's nb FINISHED slots with score = sum / generated_length ^
         length_penalty, the best nb that do not end continue.  The loop stops when no running beam can still beat the worst finished one
         (the reference's heuristic: best running sum / current generated length ^ length_penalty; early_stopping = True: as soon as every
         finished slot is filled; "never": the optimistic bound at the maximum length when length_penalty > 0) or the length limit is reached.
-        The KV cache is reordered by beam parentage every step (index_select over its batch dimension).  Returns the best finished hypothesis
-        per row, padded with pad_token_id (eos if none)."""
+        The KV cache is reordered by beam parentage every step.  Returns the best num_return finished hypotheses per row as [B * num_return, S0 + longest],
+        padded with pad_token_id (eos if none).
+        Two routes with identical results.  On the device (beam_on_device, inside the caps of afk_beam_step, AFK_EXACT_FP32 off): _beam_search_device - the
+        step is one afk_beam_step and one afk_beam_reorder_cache behind the forward pass, captured and replayed under the use_graph rule of generate().
+        Otherwise the host loop below: torch ops over [B, nb * V], one host synchronisation and one index_select copy of the whole cache per token."""
+        from . import exact as _exact
+
         dev = self.device_
         B, S0 = ids.shape
         Kc, Vt = cache
         V = self.V
         eos = [] if eos_token_id is None else ([int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple)) else [int(eos_token_id)])
+        if self.beam_on_device and not _exact.ENABLED and ops.beam_caps_ok(nb, len(eos), V):
+            return self._beam_search_device(ids, last_hidden, cache, lo, nb, max_new, eos, pad_token_id, length_penalty, early_stopping, num_return, use_graph)
         keep = (len(eos) + 1) * nb
         rep = torch.arange(B, device=dev).repeat_interleave(nb)
         Kc, Vt = Kc.index_select(1, rep).contiguous(), Vt.index_select(1, rep).contiguous()
@@ -1298,10 +1306,61 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             st["nxt"].copy_(tok.gather(1, ri).reshape(-1))
             logits = self._decode_logits(st)
             st["cur"].add_(1)
-        best_seq, best_len = fin_seq[:, 0], fin_len[:, 0]
+        return self._beam_result(ids, fin_seq, fin_len, num_return, pad_token_id, eos)
+
+    @staticmethod
+    def _beam_result(ids, fin_seq, fin_len, n, pad_token_id, eos):
+        """the best n finished hypotheses of every row (fin_seq [B, nb, max_new], fin_len [B, nb], in ranking order) behind the prompt: [B * n, S0 + longest],
+        row b * n + k = hypothesis k of row b, padded with pad_token_id (the first eos id if none, 0 without one) - the reference's order and shape"""
+        B, _, max_new = fin_seq.shape
+        best_seq, best_len = fin_seq[:, :n].reshape(B * n, max_new), fin_len[:, :n].reshape(B * n)
         pad = pad_token_id if pad_token_id is not None else (eos[0] if eos else 0)
-        best_seq = torch.where(torch.arange(max_new, device=dev)[None] < best_len[:, None], best_seq, torch.full_like(best_seq, pad))
-        return torch.cat([ids, best_seq[:, : int(best_len.max())]], dim=1)
+        best_seq = torch.where(torch.arange(max_new, device=best_seq.device)[None] < best_len[:, None], best_seq, torch.full_like(best_seq, pad))
+        return torch.cat([ids.repeat_interleave(n, dim=0) if n > 1 else ids, best_seq[:, : int(best_len.max())]], dim=1)
+
+    beam_on_device = os.environ.get("AFK_BEAM_DEVICE", "1") == "1"   # beam search: the step's decisions and the cache move as launches of the decode step (csrc/decode_beam.hip)
+
+    @torch.no_grad()
+    def _beam_search_device(self, ids, last_hidden, cache, lo, nb, max_new, eos, pad_token_id, length_penalty, early_stopping, num_return, use_graph):
+        """_beam_search with every per-token decision on the device.  A step is _decode_logits -> afk_beam_step (log-softmax, the row's top (n_eos + 1) * nb
+        continuations, finished slots, running beams, the early-stop heuristic, {t, open} in a status word) -> afk_beam_reorder_cache (the slots written since
+        the prompt move by parentage, in place: the beams of a row share their prompt keys bit for bit) -> cur += 1; nothing in it depends on the host, so it is
+        captured at t == 2 and replayed.  Token 0 runs eagerly with the kernel of the captured steps.  The host polls the status word every 8th step (steps
+        behind the closing one write nothing) and reads the finished hypotheses back once."""
+        dev = self.device_
+        B, S0 = ids.shape
+        Kc, Vt = cache
+        rep = torch.arange(B, device=dev).repeat_interleave(nb)
+        Kc, Vt = Kc.index_select(1, rep).contiguous(), Vt.index_select(1, rep).contiguous()
+        bs = ops.beam_state(B, nb, max_new, device=dev, eos=eos, length_penalty=length_penalty, early_stopping=early_stopping)
+        st = {"cache": (Kc, Vt), "lo": lo.index_select(0, rep).contiguous(), "head": self.arena["lm_head.weight"].data,
+              "emb": self.arena[self._lm + "embed_tokens.weight"].data, "cur": torch.full((1,), S0, device=dev, dtype=torch.int32), "nxt": bs["next_token"]}
+        ops.beam_step(ops.gemm_nt(last_hidden, st["head"]).float().index_select(0, rep).contiguous(), bs, step_off=0)
+
+        def step():   # token t = cur + 1 - S0: the forward pass appends the keys of token t - 1 at slot cur, so the slots S0 .. cur move
+            logits = self._decode_logits(st)
+            ops.beam_step(logits if logits.is_contiguous() else logits.contiguous(), bs, step_base=st["cur"], step_off=1 - S0)
+            ops.beam_reorder_cache(Kc, Vt, bs["src"], st["cur"], nb=nb, S0=S0, max_new=max_new)
+            st["cur"].add_(1)
+
+        if use_graph is None:
+            use_graph = max_new > 3
+        graph = None
+        for t in range(1, max_new):
+            if t % 8 == 0 and bs["status"].tolist()[1] == 0:   # one small copy, {last step, open}
+                break
+            if use_graph and t == 2:   # step 1 ran eagerly (lazy one-time initialisation inside the library happens outside the capture)
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    step()
+                graph.replay()
+            elif graph is not None:
+                graph.replay()
+            else:
+                step()
+        fin_seq, fin_len, _, _ = ops.beam_finished(bs)
+        return self._beam_result(ids, fin_seq, fin_len, num_return, pad_token_id, eos)
 
     def _decode_logits(self, st):
         """logits [B, V] (fp32) of the position after st["nxt"]: one pass over the decoder weights, cache append at st["cur"] (not advanced here)"""
@@ -1382,7 +1441,7 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
                  do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, eos_token_id=None, pad_token_id=None, use_cache=True,
                  use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, min_p=None, typical_p=1.0,
-                 epsilon_cutoff=0.0, eta_cutoff=0.0, **kwargs):
+                 epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, **kwargs):
         """Greedy decoding, sampling or beam search (GenerationMixin.generate, transformers/generation/utils.py; do_sample with temperature /
         top_k / top_p / min_p / typical_p / epsilon_cutoff / eta_cutoff as its logits warpers apply them and in their order, drawn on the device by afk_decode_sample from a counter-based generator: seed (64 bits; None: from
         torch.seed()) and the index of the token are all the state there is, so a seed gives the same ids in eager, graph-replayed and hook-driven loops; num_beams > 1: beam search with the
@@ -1432,6 +1491,21 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         of `scores` / `logits` of a row behind its first EOS are unspecified.  Unifying the two routes is a follow-up.  Refused, by an AfkError that names the
         combination: stop strings with num_beams > 1, with use_cache=False or with AFK_EXACT_FP32=1; tokenizer= when no stop string is active.  Not covered:
         max_time, ConfidenceCriteria, user criteria objects inside the graph.
+        Beam search (num_beams > 1) runs in the decode graph like the other modes: a step is the forward pass, afk_beam_step - the fp32 log-softmax of every
+        beam plus its running score, the row's best (n_eos + 1) * num_beams continuations, the finished slots ranked by sum / length ** length_penalty, the
+        running beams, the early-stop heuristic (early_stopping False / True / "never") and a status word - and afk_beam_reorder_cache, which moves the cache
+        slots written since the prompt by beam parentage, in place (the beams of a row share their prompt keys bit for bit, so nothing else has to move and no
+        second cache is allocated).  The step is captured under the use_graph rule, the loop polls the status word every 8th step and reads the finished
+        hypotheses back once.  Where torch.topk leaves the order of EQUAL scores open this route fixes it: the lower flat index beam * V + token first.
+        Outside the kernel's caps (2 <= num_beams <= 16, (n_eos + 1) * num_beams <= 64), with AFK_EXACT_FP32=1 or with AFK_BEAM_DEVICE=0 (the class attribute
+        beam_on_device) the same search runs as a host loop of torch ops, with the same results (tests/test_beam_gpu.py).
+        num_return_sequences (keyword, else the generation config; GenerationConfig.validate's rules and messages): with beams, the best n finished
+        hypotheses of every row as [B * n, S0 + longest], row b * n + k = hypothesis k of row b, padded with pad_token_id - n > num_beams raises ValueError;
+        with do_sample, ids, features, masks and attention_mask are repeated row by row before the prefill (GenerationMixin._expand_inputs_for_generation) and
+        the draw, keyed by (step, row), makes the copies differ; greedy decoding with n > 1 raises ValueError.  Out of scope for beams, and refused as before:
+        the output object, beam_indices in compute_transition_scores and per-step beam scores; the logits processors, stop strings and hooks; beam sampling
+        (do_sample with num_beams > 1).  Follow-ups: a prefill shared between sampled copies (prefill kernels choose tiles by row count, so it would not be
+        bit-equal to the expanded call), and sharing the prompt keys between the beams of a row inside the attention kernel.
         Cache handling as
         Qwen2Attention.forward modeling_qwen2.py:213-214).  Prefill runs the prompt once and fills a per-layer KV cache; every new
         token then costs one pass over the weights and one Q=1 attention over the cache.  Batches may be LEFT padded
@@ -1469,6 +1543,7 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         elif stop_spec.eos:
             eos_token_id = list(stop_spec.eos)      # beam search, the exact path and the hook loop take lists; the graph / eager loop takes the device route
 
+        n_ret = _gout.resolve_num_return_sequences(num_return_sequences, generation_config=gc, num_beams=int(num_beams), do_sample=bool(do_sample))
         flags = _gout.resolve_output_flags(**out_kw, generation_config=gc, num_beams=int(num_beams), use_cache=bool(use_cache), exact_fp32=_exact.ENABLED)
         if int(max_new_tokens) <= 0:   # GenerationMixin refuses it as well (generation/configuration_utils.py validate())
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
@@ -1488,6 +1563,9 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             sampling = dict(temperature=float(temperature) if temperature else 1.0, top_k=int(top_k or 0), top_p=1.0 if top_p is None else float(top_p),
                             seed=(int(seed) if seed is not None else int(torch.seed())) & (2 ** 64 - 1), **warp)
         ids = input_ids.to(self.device_)
+        if n_ret > 1 and int(num_beams) == 1:   # sampled copies: GenerationMixin._expand_inputs_for_generation - every tensor input repeated row by row; the
+            expand = lambda x: x.repeat_interleave(n_ret, dim=0) if torch.is_tensor(x) else x   # draw is keyed by (step, row), so the copies differ
+            ids, input_features, input_features_mask, attention_mask = expand(ids), expand(input_features), expand(input_features_mask), expand(attention_mask)
         if not use_cache:
             if do_sample:
                 raise AfkError("generate(use_cache=False) is the greedy reference path of the tests")
@@ -1516,7 +1594,8 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
         y = self._decode_layers(x, B, S0, 0, (Kc, Vt), pos_rows, krange, fast, kv_lo=lo if padded else None)
         last = y.reshape(B, S0, -1)[:, -1, :].contiguous()
         if num_beams > 1:
-            return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), int(max_new_tokens), eos_token_id, pad_token_id, float(length_penalty), early_stopping)
+            return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), int(max_new_tokens), eos_token_id, pad_token_id, float(length_penalty), early_stopping,
+                                     num_return=n_ret, use_graph=use_graph)
         first_logits = ops.gemm_nt(last, self.arena["lm_head.weight"].data).float()
         rec = None
         if flags.collect:   # one [max_new_tokens, B, V] fp32 buffer per kind, allocated once: static memory the captured step writes a slot of

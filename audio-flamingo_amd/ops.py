@@ -900,6 +900,122 @@ def decode_stop(next_token, ids, stop_at, *, S0, max_new, status=None, step_base
     return stop_at
 
 
+BEAM_MAX_BEAMS, BEAM_MAX_KEEP = 16, 64   # AFK_BEAM_MAX_BEAMS / AFK_BEAM_MAX_KEEP of include/afk.h
+_BEAM_STATE = (("run_score", torch.float32), ("fin_score", torch.float32), ("fin_len", torch.int32), ("fin_done", torch.int32), ("fin_slot", torch.int32),
+               ("fin_seq", torch.int32), ("can_improve", torch.int32), ("bp", torch.int32), ("next_token", torch.int64), ("src", torch.int32),
+               ("status", torch.int32), ("ws", torch.int32))
+
+
+def beam_caps_ok(nb, n_eos, V):
+    """does afk_beam_step take nb beams with n_eos eos ids over a vocabulary of V?  (2 <= nb <= 16, keep = (n_eos + 1) * nb <= 64, keep <= nb * V < 2^31)"""
+    keep = (int(n_eos) + 1) * int(nb)
+    return 2 <= int(nb) <= BEAM_MAX_BEAMS and keep <= BEAM_MAX_KEEP and keep <= int(nb) * int(V) < 2 ** 31
+
+
+def beam_state(B, nb, max_new, *, device, eos=(), length_penalty=1.0, early_stopping=False):
+    """the device state of one beam search over B rows x nb beams x max_new tokens, initialised as afk_beam_step's contract asks (include/afk.h): a dict of
+    the kernel's buffers - run_score [B, nb], fin_score / fin_len / fin_done / fin_slot [B, nb], fin_seq [B, nb, max_new] (row fin_slot[b, k] holds the tokens
+    of the hypothesis ranked k), can_improve [B], bp [max_new, B, nb, 2], next_token / src [B * nb], status [2], ws - and of its constants: eos (int32 on the
+    device, or None), early (0 False, 1 True, 2 "never") and the divisor tables div / hdiv [max_new] fp32, computed here in double:
+    div[t] = (t + 1) ** length_penalty, hdiv[t] = max_new ** length_penalty under early_stopping == "never" with a positive penalty, else div[t]."""
+    B, nb, max_new = int(B), int(nb), int(max_new)
+    eos = [int(e) for e in eos]
+    if early_stopping not in (False, True, "never"):
+        raise AfkError(f"beam_state: early_stopping must be False, True or 'never', got {early_stopping!r}")
+    if B < 1 or max_new < 1 or not 2 <= nb <= BEAM_MAX_BEAMS or (len(eos) + 1) * nb > BEAM_MAX_KEEP:
+        raise AfkError(f"beam_state: B = {B}, max_new = {max_new}, {nb} beams, {len(eos)} eos ids (B, max_new >= 1, 2 <= nb <= {BEAM_MAX_BEAMS}, "
+                       f"(n_eos + 1) * nb <= {BEAM_MAX_KEEP})")
+    lp = float(length_penalty)
+    div = [float((t + 1) ** lp) for t in range(max_new)]
+    hdiv = [float(max_new ** lp)] * max_new if (early_stopping == "never" and lp > 0.0) else div
+    i32 = lambda *shape: torch.zeros(shape, device=device, dtype=torch.int32)
+    run_score = torch.full((B, nb), -1.0e9, device=device, dtype=torch.float32)
+    run_score[:, 0] = 0.0   # all beams of a row start identical: only the first one is live
+    return dict(B=B, nb=nb, max_new=max_new, n_eos=len(eos), early=2 if early_stopping == "never" else int(bool(early_stopping)),
+                eos=torch.tensor(eos, device=device, dtype=torch.int32) if eos else None,
+                div=torch.tensor(div, dtype=torch.float64).to(torch.float32).to(device), hdiv=torch.tensor(hdiv, dtype=torch.float64).to(torch.float32).to(device),
+                run_score=run_score, fin_score=torch.full((B, nb), -1.0e9, device=device, dtype=torch.float32), fin_len=i32(B, nb), fin_done=i32(B, nb),
+                fin_slot=torch.arange(nb, device=device, dtype=torch.int32).repeat(B, 1).contiguous(), fin_seq=i32(B, nb, max_new),
+                can_improve=torch.ones(B, device=device, dtype=torch.int32), bp=i32(max_new, B, nb, 2),
+                next_token=torch.zeros(B * nb, device=device, dtype=torch.int64), src=torch.arange(B * nb, device=device, dtype=torch.int32),
+                status=torch.tensor([-1, 1], device=device, dtype=torch.int32), ws=i32(int(_lib.load().afk_beam_step_workspace_ints(B, nb, len(eos)))))
+
+
+def beam_step(logits, st, *, step_base=None, step_off=0):
+    """one beam-search step for token t = *step_base + step_off on the fp32 logits [B * nb, V] (beam j of row b at b * nb + j), in one call of two launches
+    (afk_beam_step; the contract is in include/afk.h): the row's best (n_eos + 1) * nb continuations by accumulated log-probability (equal scores: the lower
+    flat index j * V + token), the finished slots, the running beams with their tokens in st["next_token"] and their parents' cache rows in st["src"], the
+    early-stop heuristic, and st["status"] = {t, open}.  st: a dict from beam_state().  A t outside [0, max_new) and a call whose status says closed write
+    nothing.  -> st"""
+    _chk(logits, torch.float32, "beam_step logits")
+    if logits.dim() != 2 or logits.stride(1) != 1 or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+        raise AfkError(f"beam_step logits: [B * nb, V] with unit column stride, got {tuple(logits.shape)} strides {logits.stride()}")
+    B, nb, max_new = int(st["B"]), int(st["nb"]), int(st["max_new"])
+    R, V = logits.shape
+    if R != B * nb:
+        raise AfkError(f"beam_step logits: {R} rows for {B} rows x {nb} beams")
+    if not beam_caps_ok(nb, st["n_eos"], V):
+        raise AfkError(f"beam_step: {nb} beams, {st['n_eos']} eos ids, V = {V} (2 <= nb <= {BEAM_MAX_BEAMS}, keep = (n_eos + 1) * nb <= {BEAM_MAX_KEEP}, "
+                       f"keep <= nb * V < 2^31)")
+    sizes = dict(run_score=R, fin_score=R, fin_len=R, fin_done=R, fin_slot=R, fin_seq=R * max_new, can_improve=B, bp=2 * max_new * R, next_token=R, src=R,
+                 status=2, ws=int(_lib.load().afk_beam_step_workspace_ints(B, nb, int(st["n_eos"]))))
+    for name, dt in _BEAM_STATE + (("div", torch.float32), ("hdiv", torch.float32)):
+        t_ = st.get(name)
+        if t_ is None:
+            raise AfkError(f"beam_step: the state holds no {name} (ops.beam_state builds it)")
+        _chk(t_, dt, f"beam_step {name}")
+        if t_.numel() < sizes.get(name, max_new) or not t_.is_contiguous():
+            raise AfkError(f"beam_step {name}: a contiguous tensor of at least {sizes.get(name, max_new)} elements, got {tuple(t_.shape)}")
+    eos = st.get("eos")
+    if (0 if eos is None else eos.numel()) != int(st["n_eos"]):
+        raise AfkError(f"beam_step eos: {st['n_eos']} ids announced, got {None if eos is None else tuple(eos.shape)}")
+    if eos is not None:
+        _chk(eos, torch.int32, "beam_step eos")
+        if not eos.is_contiguous():
+            raise AfkError("beam_step eos: a contiguous int32 list")
+    if step_base is not None:
+        _chk(step_base, torch.int32, "beam_step step_base")
+        if step_base.numel() < 1 or not step_base.is_contiguous():
+            raise AfkError(f"beam_step step_base: a contiguous tensor of at least 1 element, got {tuple(step_base.shape)}")
+    _lib.call("afk_beam_step", logits.data_ptr(), logits.stride(0) if R > 1 else V, B, nb, V, max_new, _p(step_base), int(step_off), _p(eos) if eos is not None else None,
+              int(st["n_eos"]), int(st["early"]), st["div"].data_ptr(), st["hdiv"].data_ptr(), st["run_score"].data_ptr(), st["fin_score"].data_ptr(),
+              st["fin_len"].data_ptr(), st["fin_done"].data_ptr(), st["fin_slot"].data_ptr(), st["fin_seq"].data_ptr(), st["can_improve"].data_ptr(),
+              st["bp"].data_ptr(), st["next_token"].data_ptr(), st["src"].data_ptr(), st["status"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel(), _stream())
+    return st
+
+
+def beam_finished(st):
+    """-> (seq [B, nb, max_new] int64, len [B, nb] int64, score [B, nb] fp32, done [B, nb] bool): the finished hypotheses of a beam_state in ranking order (the
+    token rows gathered through fin_slot); entries of a hypothesis behind its length are unspecified"""
+    B, nb, max_new = int(st["B"]), int(st["nb"]), int(st["max_new"])
+    slot = st["fin_slot"].view(B, nb).long().clamp(0, nb - 1)
+    seq = st["fin_seq"].view(B, nb, max_new).gather(1, slot[:, :, None].expand(B, nb, max_new)).long()
+    return seq, st["fin_len"].view(B, nb).long(), st["fin_score"].view(B, nb).clone(), st["fin_done"].view(B, nb) != 0
+
+
+def beam_reorder_cache(Kc, Vt, src, cur, *, nb, S0, max_new):
+    """the KV cache moved by beam parentage in place (afk_beam_reorder_cache; the contract is in include/afk.h): Kc [L, B * nb, Smax, Hkv * D] and
+    Vt [L, B * nb, Hkv, D, pad64(Smax)] bf16, src [B * nb] int32 = each beam's parent as a flat cache row (clamped into its own row's group), cur: int32 on the
+    device - the slots S0 .. *cur move, the prompt slots (shared by a row's beams bit for bit) and everything behind *cur stay.  -> (Kc, Vt)"""
+    _chk(Kc, BF16, "beam_reorder_cache Kc"), _chk(Vt, BF16, "beam_reorder_cache Vt")
+    nb = int(nb)
+    if Kc.dim() != 4 or Vt.dim() != 5 or not Kc.is_contiguous() or not Vt.is_contiguous():
+        raise AfkError(f"beam_reorder_cache: contiguous Kc [L, R, Smax, Hkv * D] and Vt [L, R, Hkv, D, spad], got {tuple(Kc.shape)} and {tuple(Vt.shape)}")
+    L, R, Smax, nk = Kc.shape
+    _, _, Hkv, D, spad = Vt.shape
+    if tuple(Vt.shape[:2]) != (L, R) or Hkv * D != nk or spad < Smax or nb < 2 or R % nb:
+        raise AfkError(f"beam_reorder_cache: Kc {tuple(Kc.shape)} and Vt {tuple(Vt.shape)} do not describe one cache of rows in groups of {nb}")
+    if int(S0) < 0 or int(max_new) < 1 or int(S0) + int(max_new) > Smax:
+        raise AfkError(f"beam_reorder_cache: S0 + max_new = {int(S0)} + {int(max_new)} slots in a cache of {Smax}")
+    for t_, n, name in ((src, R, "src"), (cur, 1, "cur")):
+        _chk(t_, torch.int32, f"beam_reorder_cache {name}")
+        if t_.numel() < n or not t_.is_contiguous():
+            raise AfkError(f"beam_reorder_cache {name}: a contiguous tensor of at least {n} elements, got {tuple(t_.shape)}")
+    _lib.call("afk_beam_reorder_cache", Kc.data_ptr(), Vt.data_ptr(), L, R // nb, nb, Smax, spad, Hkv, D, int(S0), int(max_new), src.data_ptr(), cur.data_ptr(),
+              _stream())
+    return Kc, Vt
+
+
 # ---------------------------------------------------------------------------------------------- loss
 def count_valid(labels):
     out = torch.empty(1, device=labels.device, dtype=torch.float32)

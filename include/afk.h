@@ -480,6 +480,48 @@ int afk_decode_process(float* logits, int64_t ld_logits, int B, int V, int* hist
 int afk_decode_stop(int64_t* next_token, int B, int* ids, int64_t ld_ids, int S0, int max_new, int* stop_at, int* status, const int* step_base, int step_off,
                     const int* eos, int n_eos, int pad, int feed_pad, const int* table, int rows, int vec, int P, int E, int S, const int* target_lens, int W,
                     void* stream);
+/* One step of beam search on the device (csrc/decode_beam.hip; generate(num_beams > 1)): what GenerationMixin._beam_search does between two forward passes
+ * (transformers/generation/utils.py: _get_top_k_continuations, _update_finished_beams, _get_running_beams_for_next_iteration, _check_early_stop_heuristic,
+ * _beam_search_has_unfinished_sequences), ONE call per generated token - two launches, a block per (row, beam) and a block per row - with no host state.
+ * Enqueue-only, no allocation, capturable.  t = *step_base + step_off = the index of the token being selected (step_base: device int32, null = 0; the convention
+ * of afk_decode_sample).  A t outside [0, max_new), or a call whose status[1] is 0, returns before its first store (the workspace included): replays behind the
+ * closing step move nothing.  logits [B * nb][V] fp32 (row stride ld_logits) = the next-token logits of beam j of row b at b * nb + j.  With keep = (n_eos + 1) * nb:
+ *   1. score of continuation (j, i) = ((z - max) - log sum exp(z - max)) + run_score[b][j], all fp32, z = the logit with NaN counted as -inf; the sum is the integer
+ *      sum of round(exp(z - max) * 2^40) (no order in it: eager and replayed launches give the same bits); a NaN score, and every score of a beam whose row has no
+ *      finite maximum, counts as -inf.
+ *   2. the top keep of the row's nb * V continuations, score descending; equal scores in ascending flat index j * V + i (torch.topk leaves that order open; this
+ *      one is fixed).  parent = flat / V, token = flat % V.
+ *   3. candidate c ends when its token is in eos[n_eos], or when t + 1 == max_new.
+ *   4. finished slots: [the nb slots, the candidates c < nb with score * (1 / div[t]) and -1e9 added when (early_stopping == 1 and every slot of the row is
+ *      filled) or can_improve[b] == 0 or c does not end] ranked by score descending, equal scores in that listing's order; the first nb are the new slots
+ *      (fin_score, fin_len = t + 1, fin_done = 1 for an entering hypothesis).  Position k of the ranking keeps its tokens in row fin_slot[b][k] of fin_seq
+ *      [B * nb][max_new]: an entering hypothesis takes the row of one that left and is written there from the back-pointer records; no row is ever copied.
+ *   5. running beams: the candidates with -1e9 added to the ending ones, ranked the same way; the first nb give run_score, next_token[b * nb + j] = token,
+ *      src[b * nb + j] = b * nb + parent, and the record bp[t][b][j] = {token, parent} (bp: [max_new][B][nb][2] int32, 8-byte aligned).
+ *   6. t + 1 < max_new: can_improve[b] &= any over the new slots k of (run_score[b][0] * (1 / hdiv[t]) > (fin_done[b][k] ? min_k fin_score[b] : -1e9)).
+ *   7. status[0] = t; status[1] = open = t + 1 < max_new and some row can improve and not (early_stopping == 1 and every slot of every row is filled) - 0 where the
+ *      host loop breaks.  A step that closes also sets src to the identity (the host loop breaks in front of its cache move).
+ * div / hdiv: [max_new] fp32 tables the host computes in double - div[t] = (t + 1) ^ length_penalty, hdiv[t] = the heuristic's divisor (the same, or
+ * max_new ^ length_penalty under early_stopping == "never" with a positive penalty).  The products with 1 / div are what torch's tensor / scalar evaluates.
+ * The caller initialises: run_score = {0, -1e9 ...} per row, fin_score = -1e9, fin_len = fin_done = 0, fin_slot[b][k] = k, can_improve = 1, status = {-1, 1},
+ * ws = zeros (afk_beam_step_workspace_ints words of int32; the launches leave its counter at zero).  early_stopping: 0 False, 1 True, 2 "never".
+ * Refused: null pointers, nb outside [2, AFK_BEAM_MAX_BEAMS], keep > AFK_BEAM_MAX_KEEP, nb * V < keep or >= 2^31, a workspace that is too small. */
+#define AFK_BEAM_MAX_BEAMS 16
+#define AFK_BEAM_MAX_KEEP 64
+int64_t afk_beam_step_workspace_ints(int B, int nb, int n_eos);
+int afk_beam_step(const float* logits, int64_t ld_logits, int B, int nb, int V, int max_new, const int* step_base, int step_off, const int* eos, int n_eos,
+                  int early_stopping, const float* div, const float* hdiv, float* run_score, float* fin_score, int* fin_len, int* fin_done, int* fin_slot,
+                  int* fin_seq, int* can_improve, int* bp, int64_t* next_token, int* src, int* status, int* ws, int64_t ws_ints, void* stream);
+/* The KV cache moved by beam parentage, in place and without scratch memory (csrc/decode_beam.hip): for every layer, batch row b, beam j and slot s in
+ * [S0, min(*cur, S0 + max_new - 1)], beam j's slot becomes what beam src[b * nb + j] - b * nb held (each entry clamped into its own row's group [0, nb): a bad
+ * value never indexes outside the cache).  Only this tail moves: the beams of a row share their prompt slots bit for bit.  kcache [L][B * nb][Smax][Hkv * D],
+ * vtcache [L][B * nb][Hkv][D][spad] bf16, contiguous and 16-byte aligned.  A thread owns one 16-byte chunk of one (layer, row, slot) - for vtcache one aligned run
+ * of 8 slots of one (layer, row, head, d) line, moved slot by slot where it crosses an end of the tail - across all nb beams: it loads the nb values into
+ * registers, then stores them; no other thread touches those addresses.  The grid covers max_new slots and *cur is a device int, so the launch replays; a row
+ * whose src is the identity is skipped; slots below S0 and above *cur are never written.  Refused: null pointers, nb outside [2, AFK_BEAM_MAX_BEAMS],
+ * Hkv * D % 8 != 0, S0 + max_new > Smax, Smax > spad, spad % 8 != 0, unaligned caches. */
+int afk_beam_reorder_cache(void* kcache, void* vtcache, int L, int B, int nb, int Smax, int spad, int Hkv, int D, int S0, int max_new, const int* src,
+                           const int* cur, void* stream);
 /* The same launches for 2 .. 8 sequences decoded together (one new position each; the weights are still read once per step): M input rows h [M][K] (row stride
  * ldh) that are ALREADY normalised where the Linear follows a norm (Qwen2DecoderLayer :270 / :294, Qwen2Model.norm); pos[M] = position of each sequence's new token,
  * *start_dev = the cache slot all of them write; q_out [M][Hq*D] (row stride ldq); k_bs / vt_bs = batch strides of the K / V^T caches (elements).  Rounding points as above. */
