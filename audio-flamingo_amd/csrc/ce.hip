@@ -41,6 +41,8 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(bf16* __restrict__ logi
             f[e] = (float)t[e];
             mx = fmaxf(mx, f[e]);
         }
+        // nothing finite yet (masked vocabulary: -inf logits): exp(-inf - -inf) is NaN, for the terms and for the rescale; the sum stays 0
+        if (mx == -INFINITY) continue;
         float acc = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc += __expf(f[e] - mx);
@@ -50,6 +52,7 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(bf16* __restrict__ logi
     for (int c = nv * 8 + tid; c < V; c += 256) {
         const float f = (float)x[c];
         const float mx = fmaxf(m, f);
+        if (mx == -INFINITY) continue;
         s = s * __expf(m - mx) + __expf(f - mx);
         m = mx;
     }

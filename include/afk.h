@@ -562,7 +562,8 @@ int afk_decode_chain_lm_head_batched(const void* h, int64_t ldh, int M, const vo
 
 /* ---- loss: ForCausalLMLoss / fixed_cross_entropy, loss/loss_utils.py:33-72 ----------------------------- 
  * logits chunk [rows, V] bf16 is overwritten with d(loss)/d(logits) when write_grad; row_loss[rows] fp32;
- * denom = device scalar (number of valid labels, or num_items_in_batch). */
+ * denom = device scalar (number of valid labels, or num_items_in_batch).  Rows are ld apart (ld % 8 == 0), only their first V columns
+ * are read or written.  -inf logits (a masked vocabulary) are fine wherever the label's own logit is finite; +inf / NaN are not. */
 int afk_ce_fwd_bwd(void* logits, int64_t ld, int64_t rows, int V, const int64_t* shift_labels, float* row_loss,
                    const float* denom, float upstream, int write_grad, void* stream);
 int afk_count_valid(const int64_t* labels, int64_t n, float* out, void* stream);

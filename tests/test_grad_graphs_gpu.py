@@ -182,6 +182,59 @@ def test_accumulation_matches_sum_of_micro_batches(dev, monkeypatch, fuse, form,
     assert all(k in parts[0] for k in acc) and not any("audio_tower" in k for k in parts[2])
 
 
+LOSS_CHUNK, LOSS_LABELLED = 128, 356
+_CHUNK_ORACLE = {}
+
+
+@pytest.mark.parametrize("form", ["nt", "wgrad_direct", "direct"])
+def test_loss_head_chunk_loop_matches_oracle(dev, monkeypatch, form):
+    """functional.LMHeadLossFn with its chunk loop running three times, the last chunk ragged (356 labelled rows in chunks of 128: 128, 128,
+    100): the lm_head weight gradient accumulates across chunks, the label and row-loss slices follow the chunk.  One audio window plus text;
+    every parameter gradient against fp32 autograd through the oracle, the loss within LOSS_ATOL"""
+    import audio_flamingo_amd.functional as F
+    from tests._tol import LOSS_ATOL
+
+    _set_forms(monkeypatch, True, form)
+    monkeypatch.setattr(F.LMHeadLossFn, "CHUNK", LOSS_CHUNK)
+    g = torch.Generator().manual_seed(33)
+    feats = (torch.randn(1, 128, 3000, generator=g) * 0.5).to(BF)
+    fm = torch.zeros(1, 3000, dtype=torch.int32)
+    fm[0, :600] = 1                                     # 150 audio tokens
+    ids = torch.randint(0, 1000, (1, 2 + 150 + 360), generator=g)
+    ids[0, 2:152] = 1023
+    labels = torch.full_like(ids, -100)
+    labels[:, -LOSS_LABELLED:] = ids[:, -LOSS_LABELLED:]
+    kw = dict(input_ids=ids, input_features=feats, input_features_mask=fm, labels=labels)
+    n_labelled = int((labels[:, 1:] != -100).sum())     # rows whose shifted label counts
+    sizes = [min(LOSS_CHUNK, n_labelled - s) for s in range(0, n_labelled, LOSS_CHUNK)]
+    assert n_labelled == LOSS_LABELLED and len(sizes) >= 3 and sizes[-1] < LOSS_CHUNK, (n_labelled, sizes)
+    seen = []
+    real = F.ops.ce_fwd_bwd_
+
+    def spy(logits, *a, **k):
+        seen.append(logits.shape[0])
+        return real(logits, *a, **k)
+
+    monkeypatch.setattr(F.ops, "ce_fwd_bwd_", spy)
+    m = _fresh_model(dev)
+    m.zero_grad()
+    loss = m(**_on(kw, dev)).loss
+    loss.backward()
+    m.arena.join_streams()
+    torch.cuda.synchronize()
+    assert seen == sizes, (seen, sizes)
+    if not _CHUNK_ORACLE:   # the same weights (seed) and batch for every form: one oracle run serves all three
+
+        def objective(fwd):
+            _CHUNK_ORACLE["loss"] = fwd(**kw)["loss"]
+            return _CHUNK_ORACLE["loss"]
+
+        _CHUNK_ORACLE["leaves"] = _oracle_grads(m, objective)
+    got, want = float(loss.detach()), float(_CHUNK_ORACLE["loss"].detach())
+    assert abs(got - want) <= LOSS_ATOL, (got, want)
+    _check_oracle(m, _CHUNK_ORACLE["leaves"], ("loss head in chunks", form))
+
+
 @pytest.mark.parametrize("last", [1, 2], ids=["audio_only_last", "text_only_last"])
 def test_last_micro_step_under_backward_overlap_matches_serial(dev, last):
     """plain micro-steps, then the LAST one under BackwardOverlap + FusedAdamW (per-bucket AdamW inside backward): parameters bit-identical to

@@ -1608,6 +1608,47 @@ def test_cross_entropy(dev):
     _cmp("dlogits", work, lr.grad, atol=2e-4, rtol=2e-2)
 
 
+def _bf16_order(t):
+    """bf16 -> int32 that counts representable values in order (sign-magnitude bits unfolded; -0 and +0 both 0): adjacent values differ by 1"""
+    b = t.view(torch.int16).to(torch.int32)
+    return torch.where(b < 0, -(b & 0x7FFF), b)
+
+
+@pytest.mark.parametrize("n", [8, 8 * (4096 * 256 + 3)], ids=["one_vector", "past_the_grid_cap"])
+@pytest.mark.parametrize("a", [0.0, 1.0, -0.37])
+def test_scale_add(dev, n, a):
+    """y = (accumulate ? y : 0) + a * x with the scale read from the device, as both loss-head backward passes apply the upstream gradient.
+    n = 8 * (4096 * 256 + 3): three vectors more than the capped grid of 4096 blocks covers in one stride.  Overwrite mode is one fp32 product
+    rounded once: bit-equal to torch.  Accumulate mode may contract to a fused multiply-add: within one bf16 value of the float64 result
+    rounded to bf16.  Both modes also in place (x is y).  y carries the sign of -x: with a = 1 the sum cancels (exactly, the product being
+    exact), with a = -0.37 it does not - there an uncontracted product's own fp32 rounding, 2^-24 |a x|, would otherwise be many ulps of a
+    sum that cancelled to nearly nothing, which says nothing about the kernel."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(n % 1000 + 1)
+    x = (torch.randn(n, generator=g) * 2.0).to(BF).to(dev)
+    y0 = (torch.randn(n, generator=g) * 2.0).abs().to(BF).to(dev) * -torch.sign(x)
+    scale = torch.tensor([a], device=dev, dtype=torch.float32)
+    prod = (scale * x.float()).to(BF)
+    y = torch.full_like(y0, float("nan"))                         # overwrite mode must not read y
+    assert ops.scale_add_(x, y, scale, accumulate=False) is y
+    assert torch.equal(y, prod), "scale_add_ overwrite != (a * x) rounded to bf16"
+    xi = x.clone()
+    ops.scale_add_(xi, xi, scale, accumulate=False)
+    assert torch.equal(xi, prod), "scale_add_ overwrite in place"
+
+    def close(got, ref64, what):
+        d = (_bf16_order(got) - _bf16_order(ref64.to(BF))).abs()
+        assert int(d.max()) <= 1, (what, int((d > 1).sum()), int(d.max()))
+
+    y = y0.clone()
+    ops.scale_add_(x, y, scale, accumulate=True)
+    close(y, y0.double() + scale.double() * x.double(), "scale_add_ accumulate")
+    assert torch.equal(ops.scale_add_(x, y0.clone(), scale, accumulate=True), y), "scale_add_ not bit-deterministic"
+    xi = x.clone()
+    ops.scale_add_(xi, xi, scale, accumulate=True)
+    close(xi, x.double() + scale.double() * x.double(), "scale_add_ accumulate in place")
+
+
 # ------------------------------------------------------------------------------------------------ AdamW
 def test_adamw(dev):
     ops = _ops()
