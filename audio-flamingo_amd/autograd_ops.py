@@ -41,6 +41,7 @@ def linear(x, w, b=None, residual=None):
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, eps):
+        x = x.contiguous()   # the kernels take dense rows (ops asserts it); a no-op for the model's own activations
         y, mean, rstd = ops.layernorm_fwd(x, w, b, eps)
         ctx.save_for_backward(x, w, mean, rstd)
         return y
@@ -60,6 +61,7 @@ def layer_norm(x, w, b, eps=1e-5):
 class _RMSNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, eps):
+        x = x.contiguous()   # the kernels take dense rows (ops asserts it); a no-op for the model's own activations
         y, rstd = ops.rmsnorm_fwd(x, w, eps)
         ctx.save_for_backward(x, w, rstd)
         return y

@@ -523,6 +523,8 @@ extern "C" int afk_layernorm_bwd(const void* x, const void* w, const void* dy, c
     AFK_NORM_BWD_ALIGN("afk_layernorm_bwd");
     AFK_REQUIRE((uintptr_t)db % 8 == 0, "afk_layernorm_bwd: db must be 8-byte aligned");
     const bool cols = norm_bwd_use_cols(D);
+    // the row-per-wave form keeps a row in at most 7 x 64 x 8 (14 x 64 x 4) = 3584 columns of registers: wider rows belong to the column-owned form only
+    AFK_REQUIRE(cols || D <= 3584, "afk_layernorm_bwd: D=%d > 3584 is not served by the row-per-wave form (AFK_NORM_BWD=rows)", D);
     const int nb = std::min(cols ? norm_bwd_cols_blocks(rows, D, false) : norm_bwd_rowwave_blocks(rows), afk_norm_bwd_blocks(rows));
     hipStream_t st = (hipStream_t)stream;
     if (cols) launch_bwd_cols<false>(x, w, dy, mean, rstd, dx, dx_add, workspace, nb, rows, D, st);
@@ -629,6 +631,8 @@ extern "C" int afk_rmsnorm_bwd(const void* x, const void* w, const void* dy, con
     AFK_REQUIRE(D % 4 == 0 && D <= 4096 && (D <= 3584 || D % 8 == 0) && rows > 0, "afk_rmsnorm_bwd: unsupported D=%d", D);
     AFK_NORM_BWD_ALIGN("afk_rmsnorm_bwd");
     const bool cols = norm_bwd_use_cols(D);
+    // the row-per-wave form keeps a row in at most 7 x 64 x 8 (14 x 64 x 4) = 3584 columns of registers: wider rows belong to the column-owned form only
+    AFK_REQUIRE(cols || D <= 3584, "afk_rmsnorm_bwd: D=%d > 3584 is not served by the row-per-wave form (AFK_NORM_BWD=rows)", D);
     const int nb = std::min(cols ? norm_bwd_cols_blocks(rows, D, true) : norm_bwd_rowwave_blocks(rows), afk_norm_bwd_blocks(rows));
     hipStream_t st = (hipStream_t)stream;
     if (cols) launch_bwd_cols<true>(x, w, dy, nullptr, rstd, dx, dx_add, workspace, nb, rows, D, st);

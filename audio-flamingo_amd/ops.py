@@ -300,7 +300,14 @@ def transpose_heads(x, B, S, H, D, ld, spad, out=None):
 
 
 # ---------------------------------------------------------------------------------------------- norms
+def _dense(*named):
+    """the norm kernels address row r at base + r * D: a strided view would be read (and empty_like of it written) as if it were dense"""
+    for name, t in named:
+        assert t is None or t.is_contiguous(), f"{name} must be contiguous (got strides {tuple(t.stride())} for shape {tuple(t.shape)})"
+
+
 def layernorm_fwd(x, w, b, eps=1e-5):
+    _dense(("layernorm x", x))
     _chk(x, BF16, "layernorm x")
     D = x.shape[-1]
     rows = x.numel() // D
@@ -319,6 +326,7 @@ def _norm_ws(rows, D, device):
 
 def layernorm_bwd(x, w, dy, mean, rstd, dw, db, *, dx_add=None, accumulate=False, colsum_out=None, colsum_accumulate=False):
     """colsum_out (with dx_add, D % 8 == 0): also colsum_out[c] (+)= sum_r dx[r][c] - the bias gradient of the Linear whose output this norm normalised"""
+    _dense(("layernorm_bwd x", x), ("layernorm_bwd dy", dy), ("layernorm_bwd dx_add", dx_add))
     D = x.shape[-1]
     rows = x.numel() // D
     dx = torch.empty_like(x)
@@ -336,6 +344,7 @@ def layernorm_bwd(x, w, dy, mean, rstd, dw, db, *, dx_add=None, accumulate=False
 
 
 def rmsnorm_fwd(x, w, eps=1e-6):
+    _dense(("rmsnorm x", x))
     _chk(x, BF16, "rmsnorm x")
     D = x.shape[-1]
     rows = x.numel() // D
@@ -346,6 +355,7 @@ def rmsnorm_fwd(x, w, eps=1e-6):
 
 
 def rmsnorm_bwd(x, w, dy, rstd, dw, *, dx_add=None, accumulate=False):
+    _dense(("rmsnorm_bwd x", x), ("rmsnorm_bwd dy", dy), ("rmsnorm_bwd dx_add", dx_add))
     D = x.shape[-1]
     rows = x.numel() // D
     dx = torch.empty_like(x)
