@@ -78,7 +78,9 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
         for (int f = tid / nmel; f < FT; f += fstep) {
             float acc = 0.f;
             for (int kk = 0; kk < NBIN; ++kk) acc = fmaf(melT[kk * nmel + m], pw[f][kk], acc);
-            const float v = log10f(fmaxf(acc, 1e-10f));
+            // log10(max(acc, 1e-10)): the floored value is -10 exactly, as in the oracle (log10f(1e-10f) itself comes out one ulp below -10, so a
+            // silent window would read -1.5000002 instead of -1.5)
+            const float v = acc > 1e-10f ? log10f(acc) : -10.f;
             lm[m][f] = v;
             if (f0 + f < T) lmax = fmaxf(lmax, v);
         }
