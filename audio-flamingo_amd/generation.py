@@ -1,0 +1,552 @@
+"""generate() of the MI355X-native Audio Flamingo 3 model: greedy decoding, sampling and beam search on the KV cache, host code only (docs/generate.md
+tells the routes feature by feature; the forward pieces a step runs - _decode_logits, _decode_layers*, _chain_* - live in modeling.py).
+
+  DecodeState        the record a decode step works on: the cache, the static device tensors, what the step applies
+  _run_steps         the loop every route drives its step with: eager, captured at the second step, replayed, polled every eighth
+  AfkGenerationMixin generate() and its routes, inherited by AudioFlamingo3ForConditionalGeneration"""
+from __future__ import annotations
+
+import os
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import _lib, ops
+from . import decode_process as _process
+from . import decode_stop as _stop
+from ._lib import AfkError
+
+
+@dataclass
+class SingleSequence:
+    """one sequence: cur, position and the key-range end live in ONE device tensor, advanced by one add per step"""
+    state: torch.Tensor     # int32 [4] = [lo, key-range end, cache slot, position]
+    kr1: torch.Tensor       # state[0:2], the key range the attention reads
+    pos1: torch.Tensor      # state[3:4], the rotary position
+    advance: torch.Tensor   # state[1:4], what a step moves
+
+
+@dataclass
+class OnDevice:
+    """one sequence with token selection and step bookkeeping on the device: the static buffers of that step"""
+    x0: torch.Tensor                          # the embedding row of the token just selected: the next step's input
+    tok_buf: torch.Tensor                     # int64 [max_new_tokens], the emitted tokens
+    logits: Optional[torch.Tensor] = None     # fp32 [1, V]: sampled, processed or recorded steps
+    part_val: Optional[torch.Tensor] = None   # plain greedy: the lm_head launch's (max, argmax) per eight rows
+    part_idx: Optional[torch.Tensor] = None
+
+
+@dataclass
+class DecodeState:
+    """what one decode step reads and writes; everything position-dependent is on the device, so the step can be captured.  A record: no behaviour."""
+    cache: tuple            # (K, Vt) as AfkKVCache holds them
+    lo: torch.Tensor        # int32 [B], first real position of every row
+    head: torch.Tensor      # lm_head weight
+    emb: torch.Tensor       # embed_tokens weight
+    cur: torch.Tensor       # int32 [1], the cache slot the step appends at
+    nxt: torch.Tensor       # int64 [B], the token just selected
+    sampling: Optional[dict] = None   # the warpers and the seed (generate()); None: greedy
+    proc: Optional[dict] = None       # decode_process.build_state
+    rec: Optional[dict] = None        # {"logits", "scores"}: the [max_new_tokens, B, V] buffers of the output object
+    stop: Optional[dict] = None       # decode_stop.build_state
+    aws: Optional[torch.Tensor] = None   # workspace of the Q = 1 attention (allocated by the first step that needs it)
+    tok_off: Optional[int] = None     # token number = *cur + tok_off
+    single: Optional[SingleSequence] = None
+    on_device: Optional[OnDevice] = None
+
+
+def _run_steps(step, max_new, use_graph, closed, after=None):
+    """steps 1 .. max_new - 1 of a decode loop (token 0 is the caller's) -> the number of steps run.  Step 1 runs eagerly (lazy one-time initialisation
+    inside the library happens outside the capture); with use_graph (None: whenever more than 3 tokens are asked for) step 2 is captured into a HIP graph
+    and replayed from then on.  closed(t) is asked in front of every 8th step, and the loop ends when it says so.  after(): host work behind every
+    step, outside the capture."""
+    if use_graph is None:
+        use_graph = max_new > 3
+    graph, n = None, 0
+    for t in range(1, max_new):
+        if t % 8 == 0 and closed(t):
+            break
+        if use_graph and t == 2:
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                step()
+            graph.replay()  # capture only records: the step for t == 2 itself still has to run
+        elif graph is not None:
+            graph.replay()
+        else:
+            step()
+        if after is not None:
+            after()
+        n += 1
+    return n
+
+
+class AfkGenerationMixin:
+    beam_on_device = os.environ.get("AFK_BEAM_DEVICE", "1") == "1"   # beam search: the step's decisions and the cache move as launches of the decode step (csrc/decode_beam.hip)
+
+    # ------------------------------------------------------------------ the pieces of a step
+    @staticmethod
+    def _select_token(logits, sampling=None):
+        """greedy argmax, or GenerationMixin's sampling chain on the [B, V] fp32 logits of the new position: temperature -> top-k -> top-p
+        (TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper, transformers/generation/logits_process.py) -> softmax -> multinomial.
+        Token selection is O(B*V) index work outside the training hot path: plain torch ops."""
+        if not sampling:
+            return logits.argmax(-1)
+        t, k, p_, gen = sampling["temperature"], sampling["top_k"], sampling["top_p"], sampling["generator"]
+        if t and t != 1.0:
+            logits = logits / t
+        if k and k > 0:
+            kth = logits.topk(min(k, logits.shape[-1]), -1).values[..., -1:]
+            logits = logits.masked_fill(logits < kth, float("-inf"))
+        if p_ is not None and p_ < 1.0:
+            sl, si = logits.sort(-1, descending=False)
+            drop = sl.softmax(-1).cumsum(-1) <= (1.0 - p_)
+            drop[..., -1:] = False  # always keep the most likely token
+            logits = logits.masked_fill(drop.scatter(-1, si, drop), float("-inf"))
+        return torch.multinomial(logits.softmax(-1), 1, generator=gen).squeeze(-1)
+
+    @staticmethod
+    def _record_rows(rec, which, rows, *, step_base=None, step_off=0):
+        """generate(output_logits / output_scores): one afk_decode_record launch that keeps the fp32 rows [B, V] in slot *step_base + step_off of rec[which]
+        ([max_new_tokens, B, V]).  Nothing is enqueued when the buffer was not asked for, or when `scores` shares the buffer of `logits` (greedy decoding with
+        no processor: the row is recorded once, under "logits")."""
+        if not rec or rec.get(which) is None or (which == "scores" and rec.get("logits") is rec["scores"]):
+            return
+        if rows.dtype != torch.float32 or rows.stride(-1) != 1:   # only what a user logits_processor returned (token 0 and the eager hook loop): the captured
+            rows = rows.float().contiguous()                      # steps hand over the fp32 rows the lm_head wrote, so nothing is allocated or copied there
+        ops.decode_record(rows, rec[which], step_base=step_base, step_off=step_off)
+
+    @staticmethod
+    def _scores_kw(rec):
+        """the sampler's keywords that make its launch keep the warped row (afk_decode_sample_scored); {} when scores were not asked for"""
+        return dict(scores_out=rec["scores"]) if rec and rec.get("scores") is not None else {}
+
+    @staticmethod
+    def _sample_token(logits, sampling, **kw):
+        """the sampling chain of _select_token on the device, in one launch and with no host state (ops.decode_sample): temperature -> top-k -> top-p ->
+        min_p -> typical_p -> epsilon_cutoff -> eta_cutoff -> the draw from a counter-based generator keyed by sampling["seed"]; kw: the draw's counter
+        (step_base / step_off) and the outputs.  Every sampled token of generate() - the first, the batched step, the one-sequence chain, the hook loop - comes
+        through here with the same `sampling` dict."""
+        if logits.dtype != torch.float32 or logits.stride(-1) != 1:
+            logits = logits.float().contiguous()
+        return ops.decode_sample(logits, temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"], seed=sampling["seed"],
+                                 min_p=sampling["min_p"], typical_p=sampling["typical_p"], epsilon_cutoff=sampling["epsilon_cutoff"],
+                                 eta_cutoff=sampling["eta_cutoff"], **kw)
+
+    def _record_and_process(self, st, logits, *, step_base=None, step_off=0, **select):
+        """the front of every route's token: the raw row recorded in front of the processors, then the built-in processors in place (`select`: the launch
+        also selects greedily from the row it leaves and does the step's bookkeeping, ops.decode_process)"""
+        self._record_rows(st.rec, "logits", logits, step_base=step_base, step_off=step_off)
+        if st.proc:   # the token being generated is number cur + 1 - S0: the processors' (and the draw's) counter lives on the device and advances with the step
+            _process.apply(st.proc, logits, next_token=st.nxt, step_base=step_base, step_off=step_off, **select)
+
+    def _pick_token(self, st, logits, *, step_base=None, step_off=0, record=True, out=None, **book):
+        """the token of the processed rows, into `out` where given: the draw (whose launch keeps the warped row where scores were asked for; book: the
+        bookkeeping it does for a single sequence), or the row recorded as the step's score and its argmax"""
+        if st.sampling:
+            return self._sample_token(logits, st.sampling, step_base=step_base, step_off=step_off, out=out, **book, **self._scores_kw(st.rec))
+        if record:
+            self._record_rows(st.rec, "scores", logits, step_base=step_base, step_off=step_off)
+        tok = self._select_token(logits)
+        return tok if out is None else out.copy_(tok)
+
+    def _select_on_device(self, st, x):
+        """the tail of the single-sequence step whose selection stays on the device, behind the layers' residual row x: the lm_head launch, then ONE launch
+        for argmax or the draw / the token / the positions / the next embedding row"""
+        od, rec, off = st.on_device, st.rec, st.tok_off
+        book = dict(tokens_out=od.tok_buf, tok_off=off, state=st.single.state, emb=st.emb, x_out=od.x0)
+        if st.sampling or st.proc:
+            # sampled, or logits processors: the lm_head launch writes the fp32 logits; the processors' launch edits the row (and, greedy, selects from it and
+            # does the bookkeeping); the sample launch draws and does the bookkeeping
+            self._chain_lm_head(x, st.head, logits=od.logits)
+            select = {} if st.sampling else dict(select=True, **book)   # greedy: st.proc is set here
+            self._record_and_process(st, od.logits, step_base=st.cur, step_off=off, **select)
+            if select:
+                # the selecting launch has advanced state[2] (= cur) itself, and the processed row it selected from is still in place: recorded BEHIND it,
+                # one step further back (rather than inside the launch, which would put a vocabulary-sized store into afk_decode_process for this case only)
+                self._record_rows(rec, "scores", od.logits, step_base=st.cur, step_off=off - 1)
+            else:
+                self._pick_token(st, od.logits, step_base=st.cur, step_off=off, out=st.nxt, **book)
+            return
+        # plain greedy: the lm_head launch leaves (max, argmax) per eight rows, the select launch does everything up to the next step.  Flags off: no logits
+        # row is written; on: the same launch also leaves the row (the partial argmax pairs, hence the ids, are the same)
+        self._chain_lm_head(x, st.head, logits=od.logits if rec else None, part_val=od.part_val, part_idx=od.part_idx)
+        if rec:   # no processor: scores and logits are the same rows (one buffer when both are asked for); in front of the select launch, which advances cur
+            self._record_rows(rec, "logits", od.logits, step_base=st.cur, step_off=off)
+            self._record_rows(rec, "scores", od.logits, step_base=st.cur, step_off=off)
+        _lib.call("afk_decode_select_greedy", od.part_val.data_ptr(), od.part_idx.data_ptr(), od.part_val.numel(), st.nxt.data_ptr(), od.tok_buf.data_ptr(), off,
+                  st.single.state.data_ptr(), st.emb.data_ptr(), st.emb.stride(0), st.emb.shape[1], od.x0.data_ptr(), ops._stream())
+
+    def _decode_step(self, st):
+        """one greedy or sampled decode step on static buffers (everything position-dependent lives on the device): HIP-graph capturable"""
+        if st.on_device is not None:   # one sequence: 5 launches per layer + lm_head + ONE launch for argmax or the draw / token / positions / the next embedding row
+            x = self._chain_layers(st.on_device.x0, st.cache, st.single.pos1, st.single.kr1, st.cur, aws=st.aws)
+            self._select_on_device(st, x)
+            if st.stop:   # behind the selection launch, which has advanced cur (= state[2]) already: one step back.  The next embedding row is in x0: no pad is fed
+                _stop.apply(st.stop, st.nxt, step_base=st.cur, step_off=st.tok_off - 1)
+            return
+        logits = self._decode_logits(st)
+        self._record_and_process(st, logits, step_base=st.cur, step_off=st.tok_off)
+        self._pick_token(st, logits, step_base=st.cur, step_off=st.tok_off, out=st.nxt)
+        if st.stop:   # the stopping rule on the token just selected; a row that finished earlier emits pad_token_id and the next step embeds it
+            _stop.apply(st.stop, st.nxt, step_base=st.cur, step_off=st.tok_off, feed_pad=True)
+        (st.single.advance if st.single is not None else st.cur).add_(1)   # single sequence: cur, position and the key-range end live in one tensor
+
+    def _new_state(self, cache, lo, cur, nxt, **kw):
+        return DecodeState(cache=cache, lo=lo, head=self.arena["lm_head.weight"].data, emb=self.arena[self._lm + "embed_tokens.weight"].data,
+                           cur=torch.full((1,), cur, device=self.device_, dtype=torch.int32), nxt=nxt, **kw)
+
+    # ------------------------------------------------------------------ beam search
+    @torch.no_grad()
+    def _beam_search(self, ids, last_hidden, cache, lo, nb, max_new, eos, pad, length_penalty, early_stopping, *, num_return=1, use_graph=None):
+        """Beam search on the KV cache with GenerationMixin's scoring (transformers/generation/utils.py:3008-3400): every batch row keeps `nb`
+        running beams ranked by accumulated log-probability; at each step the best (n_eos + 1) * nb continuations over all beams are drawn, the
+        ones among the top nb that end (EOS, or the length limit) compete for the row's nb FINISHED slots with score = sum / generated_length ^
+        length_penalty, the best nb that do not end continue.  The loop stops when no running beam can still beat the worst finished one
+        (the reference's heuristic: best running sum / current generated length ^ length_penalty; early_stopping = True: as soon as every
+        finished slot is filled; "never": the optimistic bound at the maximum length when length_penalty > 0) or the length limit is reached.
+        The KV cache is reordered by beam parentage every step.  eos: the ids as a tuple, pad: the id behind a hypothesis's end (decode_stop.resolve).
+        Returns the best num_return finished hypotheses per row as [B * num_return, S0 + longest], padded with pad.
+        Two routes with identical results: _beam_search_device (beam_on_device, inside the caps of afk_beam_step, AFK_EXACT_FP32 off), otherwise the
+        host loop below: torch ops over [B, nb * V], one host synchronisation and one index_select copy of the whole cache per token."""
+        from . import exact as _exact
+
+        dev = self.device_
+        B, S0 = ids.shape
+        V = self.V
+        rep = torch.arange(B, device=dev).repeat_interleave(nb)   # one cache row per beam
+        Kc, Vt = cache[0].index_select(1, rep).contiguous(), cache[1].index_select(1, rep).contiguous()
+        lo = lo.index_select(0, rep).contiguous()
+        if self.beam_on_device and not _exact.ENABLED and ops.beam_caps_ok(nb, len(eos), V):
+            return self._beam_search_device(ids, last_hidden, (Kc, Vt), lo, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph)
+        keep = (len(eos) + 1) * nb
+        st = self._new_state((Kc, Vt), lo, S0, torch.zeros(B * nb, device=dev, dtype=torch.int64))
+        run_seq = torch.zeros((B, nb, max_new), device=dev, dtype=torch.int64)
+        run_score = torch.full((B, nb), -1.0e9, device=dev, dtype=torch.float32)
+        run_score[:, 0] = 0.0                                           # all beams of a row start identical: only the first one is live
+        fin_seq = torch.zeros((B, nb, max_new), device=dev, dtype=torch.int64)
+        fin_len = torch.zeros((B, nb), device=dev, dtype=torch.int64)
+        fin_score = torch.full((B, nb), -1.0e9, device=dev, dtype=torch.float32)
+        fin_done = torch.zeros((B, nb), device=dev, dtype=torch.bool)
+        logits = ops.gemm_nt(last_hidden, st.head).float().index_select(0, rep)      # next-token logits after the prompt, one copy per beam
+        top_mask = torch.arange(keep, device=dev) < nb
+        boff = (torch.arange(B, device=dev) * nb)[:, None]
+        can_improve = torch.ones((B, 1), device=dev, dtype=torch.bool)
+        for t in range(max_new):
+            logp = torch.log_softmax(logits, dim=-1).view(B, nb, V) + run_score[:, :, None]
+            cand_score, cand = logp.view(B, nb * V).topk(keep, dim=-1)
+            parent, tok = cand // V, cand % V
+            cand_seq = run_seq.gather(1, parent[:, :, None].expand(B, keep, max_new)).clone()
+            cand_seq[:, :, t] = tok
+            ends = torch.zeros_like(tok, dtype=torch.bool)
+            for e in eos:
+                ends |= tok == e
+            if t + 1 == max_new:
+                ends[:] = True                                            # the length limit finishes whatever is left
+            # finished slots: candidates among the top nb that end, scored sum / generated_length ^ length_penalty
+            fscore = cand_score / float((t + 1) ** length_penalty)
+            full = fin_done.all(-1, keepdim=True) & (early_stopping is True)
+            fscore = fscore + (full | ~can_improve | ~(ends & top_mask[None])).float() * -1.0e9
+            ms, mi = torch.cat([fin_score, fscore], 1).topk(nb, dim=-1)
+            fin_seq = torch.cat([fin_seq, cand_seq], 1).gather(1, mi[:, :, None].expand(B, nb, max_new))
+            fin_len = torch.cat([fin_len, torch.full_like(tok, t + 1)], 1).gather(1, mi)
+            fin_done = torch.cat([fin_done, ends & top_mask[None]], 1).gather(1, mi)
+            fin_score = ms
+            # running beams: the best nb candidates that do not end
+            rs, ri = (cand_score + ends.float() * -1.0e9).topk(nb, dim=-1)
+            run_seq, run_score = cand_seq.gather(1, ri[:, :, None].expand(B, nb, max_new)), rs
+            if t + 1 == max_new:
+                break
+            # can a running beam still beat the worst finished hypothesis?  (reference heuristic, utils.py:3008-3052)
+            hyp_len = (max_new if (early_stopping == "never" and length_penalty > 0.0) else (t + 1))
+            best_running = run_score[:, :1] / float(hyp_len ** length_penalty)
+            worst_fin = torch.where(fin_done, fin_score.min(-1, keepdim=True).values, torch.full_like(fin_score, -1.0e9))
+            can_improve = can_improve & (best_running > worst_fin).any(-1, keepdim=True)
+            if not bool(can_improve.any()) or (early_stopping is True and bool(fin_done.all())):
+                break
+            # advance the model: reorder the cache by parentage, feed the chosen tokens
+            src = (parent.gather(1, ri) + boff).reshape(-1)
+            Kc.copy_(Kc.index_select(1, src)), Vt.copy_(Vt.index_select(1, src))
+            st.nxt.copy_(tok.gather(1, ri).reshape(-1))
+            logits = self._decode_logits(st)
+            st.cur.add_(1)
+        return self._beam_result(ids, fin_seq, fin_len, num_return, pad)
+
+    @staticmethod
+    def _beam_result(ids, fin_seq, fin_len, n, pad):
+        """the best n finished hypotheses of every row (fin_seq [B, nb, max_new], fin_len [B, nb], in ranking order) behind the prompt: [B * n, S0 + longest],
+        row b * n + k = hypothesis k of row b, padded with pad (0 where neither a pad nor an eos id is known) - the reference's order and shape"""
+        B, _, max_new = fin_seq.shape
+        best_seq, best_len = fin_seq[:, :n].reshape(B * n, max_new), fin_len[:, :n].reshape(B * n)
+        best_seq = torch.where(torch.arange(max_new, device=best_seq.device)[None] < best_len[:, None], best_seq, torch.full_like(best_seq, pad if pad is not None else 0))
+        return torch.cat([ids.repeat_interleave(n, dim=0) if n > 1 else ids, best_seq[:, : int(best_len.max())]], dim=1)
+
+    @torch.no_grad()
+    def _beam_search_device(self, ids, last_hidden, cache, lo, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph):
+        """_beam_search with every per-token decision on the device (cache, lo: one row per beam, rep: each one's prompt row).  A step is _decode_logits -> afk_beam_step (log-softmax, the row's top (n_eos + 1) * nb
+        continuations, finished slots, running beams, the early-stop heuristic, {t, open} in a status word) -> afk_beam_reorder_cache (the slots written since
+        the prompt move by parentage, in place: the beams of a row share their prompt keys bit for bit) -> cur += 1; nothing in it depends on the host, so it is
+        captured and replayed (_run_steps).  Token 0 runs eagerly with the kernel of the captured steps.  The host polls the status word every 8th step (steps
+        behind the closing one write nothing) and reads the finished hypotheses back once."""
+        B, S0 = ids.shape
+        Kc, Vt = cache
+        bs = ops.beam_state(B, nb, max_new, device=self.device_, eos=eos, length_penalty=length_penalty, early_stopping=early_stopping)
+        st = self._new_state(cache, lo, S0, bs["next_token"])
+        ops.beam_step(ops.gemm_nt(last_hidden, st.head).float().index_select(0, rep).contiguous(), bs, step_off=0)
+
+        def step():   # token t = cur + 1 - S0: the forward pass appends the keys of token t - 1 at slot cur, so the slots S0 .. cur move
+            logits = self._decode_logits(st)
+            ops.beam_step(logits if logits.is_contiguous() else logits.contiguous(), bs, step_base=st.cur, step_off=1 - S0)
+            ops.beam_reorder_cache(Kc, Vt, bs["src"], st.cur, nb=nb, S0=S0, max_new=max_new)
+            st.cur.add_(1)
+
+        _run_steps(step, max_new, use_graph, lambda t: bs["status"].tolist()[1] == 0)   # one small copy, {last step, open}
+        fin_seq, fin_len, _, _ = ops.beam_finished(bs)
+        return self._beam_result(ids, fin_seq, fin_len, num_return, pad)
+
+    # ------------------------------------------------------------------ generate
+    @torch.no_grad()
+    def generate(self, input_ids, input_features=None, input_features_mask=None, attention_mask=None, max_new_tokens=20,
+                 do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, eos_token_id=None, pad_token_id=None, use_cache=True,
+                 use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, repetition_penalty=1.0,
+                 no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, min_p=None, typical_p=1.0,
+                 epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, **kwargs):
+        """Greedy decoding, sampling or beam search on a KV cache, with GenerationMixin.generate's arguments and results; docs/generate.md describes every
+        route, what it launches and how it differs from the reference.
+
+        input_ids [B, S0], input_features / input_features_mask (audio, merged in the prefill), attention_mask (LEFT padding only).
+        max_new_tokens (20, > 0).  use_cache (True; False: the greedy recompute path of the tests).  use_graph (None: capture the decode step into a HIP
+        graph whenever more than 3 tokens are asked for).
+        do_sample (False) with temperature (1.0) / top_k (50; 1 is greedy) / top_p (1.0) / min_p / typical_p (1.0) / epsilon_cutoff (0.0) / eta_cutoff (0.0)
+        and seed (None: from torch.seed()): one seed gives the same ids on every route.
+        num_beams (1) with length_penalty (1.0) / early_stopping (False, True, "never"); num_return_sequences (1; needs beams or do_sample).
+        repetition_penalty (1.0) / no_repeat_ngram_size (0) / min_new_tokens (0) / suppress_tokens / begin_suppress_tokens: the built-in logits processors.
+        eos_token_id (int, list, tuple or tensor) / pad_token_id (default: the first eos id) / stop_strings= with tokenizer=.
+        logits_processor= / stopping_criteria= / streamer=: the reference's per-step hooks; with one of them the steps run eagerly.
+        return_dict_in_generate= with output_scores= / output_logits=: an AfkGenerateOutput (sequences, scores, logits, past_key_values) in place of the ids.
+        generation_config (default: self.generation_config if there is one) supplies every argument left at its default.
+
+        Returns the ids [B * num_return_sequences, S0 + n]: the prompt, then the new tokens, pad_token_id behind a row's end.
+
+        Raises ValueError where the reference's validation does (max_new_tokens <= 0, num_return_sequences, min_p / typical_p, eos / pad / stop_strings
+        forms, stop strings without a tokenizer) and AfkError for what is not built: unknown keywords, synced_gpus / use_model_defaults / assistant_model;
+        attention masks that are not left padding; beams with do_sample or use_cache=False; the logits processors, hooks, stop strings or the output
+        object with beams or with use_cache=False; stop strings or the output object with AFK_EXACT_FP32=1; tokenizer= without a stop string;
+        output_attentions / output_hidden_states."""
+        self._require_hip()
+        procs, criteria, streamer = kwargs.pop("logits_processor", None), kwargs.pop("stopping_criteria", None), kwargs.pop("streamer", None)
+        out_kw = {k: kwargs.pop(k, None) for k in ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")}
+        stop_strings, tokenizer = kwargs.pop("stop_strings", None), kwargs.pop("tokenizer", None) or None
+        for k in ("synced_gpus", "use_model_defaults", "assistant_model"):
+            if kwargs.get(k):
+                raise AfkError(f"generate({k}=...) is not supported by this implementation")
+            kwargs.pop(k, None)
+        if kwargs:
+            raise AfkError(f"generate(): unknown / unsupported arguments {sorted(kwargs)}")
+        hooks = bool(procs) or bool(criteria) or streamer is not None   # GenerationMixin's per-step callbacks: host code between the steps -> eager steps
+        gc = generation_config if generation_config is not None else getattr(self, "generation_config", None)
+        if gc is not None:  # explicit arguments win; anything still at its default is taken from the generation config
+            pick = lambda cur, default, name: getattr(gc, name, None) if (cur == default and getattr(gc, name, None) is not None) else cur
+            max_new_tokens = pick(max_new_tokens, 20, "max_new_tokens")
+            do_sample, temperature, top_k, top_p = pick(do_sample, False, "do_sample"), pick(temperature, 1.0, "temperature"), pick(top_k, 50, "top_k"), pick(top_p, 1.0, "top_p")
+            num_beams, length_penalty, early_stopping = pick(num_beams, 1, "num_beams"), pick(length_penalty, 1.0, "length_penalty"), pick(early_stopping, False, "early_stopping")
+            eos_token_id, pad_token_id = pick(eos_token_id, None, "eos_token_id"), pick(pad_token_id, None, "pad_token_id")
+        spec = _process.resolve(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, begin_suppress_tokens, eos_token_id=eos_token_id,
+                                generation_config=gc)   # the five logits processors: keyword, else generation config, validated as the reference does
+        from . import exact as _exact
+        from . import generation_output as _gout
+
+        # the stopping rule: the eos ids as a tuple, pad defaulted to the first of them, stop strings (keyword, else generation config) with their refusals.
+        # Every route below takes eos and pad in this form
+        stop_spec = _stop.resolve(eos_token_id, pad_token_id, stop_strings, tokenizer, generation_config=gc, num_beams=int(num_beams), use_cache=bool(use_cache),
+                                  exact_fp32=_exact.ENABLED)
+        eos, pad = stop_spec.eos, stop_spec.pad
+        n_ret = _gout.resolve_num_return_sequences(num_return_sequences, generation_config=gc, num_beams=int(num_beams), do_sample=bool(do_sample))
+        flags = _gout.resolve_output_flags(**out_kw, generation_config=gc, num_beams=int(num_beams), use_cache=bool(use_cache), exact_fp32=_exact.ENABLED)
+        if int(max_new_tokens) <= 0:   # GenerationMixin refuses it as well (generation/configuration_utils.py validate())
+            raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
+        if spec.active and (num_beams > 1 or not use_cache):
+            raise AfkError("generate(repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens): greedy or sampled "
+                           "decoding on the KV cache only (no num_beams > 1, no use_cache=False)")
+        if _exact.ENABLED and not do_sample and num_beams == 1 and not hooks and not spec.active and type(self).__name__ == "AudioFlamingo3ForConditionalGeneration":
+            # AFK_EXACT_FP32=1: greedy decoding by exact-fp32 recomputation of the prefix (exact.py) - the reference's greedy ids with no "confident rows" filter
+            return _exact.greedy_generate(self, input_ids, input_features, input_features_mask, attention_mask, max_new_tokens, list(eos) or None, pad)
+        if num_beams > 1 and (do_sample or not use_cache):
+            raise AfkError("generate(num_beams > 1): beam search is deterministic and runs on the KV cache (no do_sample, no use_cache=False)")
+        if hooks and (num_beams > 1 or not use_cache):
+            raise AfkError("generate(logits_processor / stopping_criteria / streamer): greedy or sampled decoding on the KV cache only")
+        sampling = None
+        warp = _process.resolve_warpers(min_p, typical_p, epsilon_cutoff, eta_cutoff, generation_config=gc, do_sample=bool(do_sample) and num_beams == 1)
+        if do_sample and int(top_k or 0) != 1:   # top_k == 1 is greedy selection (and keeps the no-logits path)
+            sampling = dict(temperature=float(temperature) if temperature else 1.0, top_k=int(top_k or 0), top_p=1.0 if top_p is None else float(top_p),
+                            seed=(int(seed) if seed is not None else int(torch.seed())) & (2 ** 64 - 1), **warp)
+        ids = input_ids.to(self.device_)
+        if n_ret > 1 and int(num_beams) == 1:   # sampled copies: GenerationMixin._expand_inputs_for_generation - every tensor input repeated row by row; the
+            expand = lambda x: x.repeat_interleave(n_ret, dim=0) if torch.is_tensor(x) else x   # draw is keyed by (step, row), so the copies differ
+            ids, input_features, input_features_mask, attention_mask = expand(ids), expand(input_features), expand(input_features_mask), expand(attention_mask)
+        if not use_cache:
+            if do_sample:
+                raise AfkError("generate(use_cache=False) is the greedy reference path of the tests")
+            return self._generate_recompute(ids, input_features, input_features_mask, attention_mask, max_new_tokens, eos)
+        B, S0 = ids.shape
+        dev = self.device_
+        max_new = int(max_new_tokens)
+        lo, padded, Kc, Vt, pos_rows, krange, fast = self._prefill_setup(attention_mask, B, S0, max_new_tokens, "generate()")
+        x = self._merged_embeddings(ids, input_features, input_features_mask)
+        y = self._decode_layers(x, B, S0, 0, (Kc, Vt), pos_rows, krange, fast, kv_lo=lo if padded else None)
+        last = y.reshape(B, S0, -1)[:, -1, :].contiguous()
+        if num_beams > 1:
+            return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), max_new, eos, pad, float(length_penalty), early_stopping, num_return=n_ret, use_graph=use_graph)
+        first_logits = ops.gemm_nt(last, self.arena["lm_head.weight"].data).float()
+        V = first_logits.shape[1]
+        rec = None
+        if flags.collect:   # one [max_new_tokens, B, V] fp32 buffer per kind, allocated once: static memory the captured step writes a slot of
+            new_buf = lambda: torch.empty((max_new, B, V), device=dev, dtype=torch.float32)
+            rec = {"logits": new_buf() if flags.logits else None, "scores": None}
+            if flags.scores:   # greedy with no processor of any kind: the reference returns the same tensors in both tuples - one buffer, one record per step
+                rec["scores"] = rec["logits"] if (flags.logits and not sampling and not spec.active and not procs) else new_buf()
+            self._record_rows(rec, "logits", first_logits, step_off=0)   # token 0, eagerly, with the kernel of the captured steps
+        proc = None
+        if spec.active:   # token 0, eagerly, with the kernel of the captured steps; in front of the user's processors (GenerationMixin._merge_criteria_processor_list)
+            proc = _process.build_state(spec, ids, max_new, V)
+            _process.apply(proc, first_logits)
+        if procs:
+            first_logits = procs(ids, first_logits)
+        if not sampling:
+            self._record_rows(rec, "scores", first_logits, step_off=0)
+        st = self._new_state((Kc, Vt), lo, S0, self._sample_token(first_logits, sampling, **self._scores_kw(rec)) if sampling else self._select_token(first_logits),
+                             sampling=sampling, tok_off=1 - S0, proc=proc, rec=rec)   # the first token is draw 0
+        stop = None
+        if stop_spec.device:   # more than one eos id, or stop strings: the rule is a launch of the step.  Token 0, eagerly, with the kernel of the captured steps
+            stop = st.stop = _stop.build_state(stop_spec, ids, max_new, _stop.build_table(tokenizer, stop_spec.stop_strings) if stop_spec.stop_strings else None)
+            _stop.apply(stop, st.nxt, step_off=0)
+        if B == 1:   # one device tensor [lo, key-range end, cache slot, position] -> the views the kernels read; one add per step moves the last three
+            state = torch.cat([lo, torch.tensor([S0 + 1, S0], device=dev, dtype=torch.int32), S0 - lo]).contiguous()
+            st.cur, st.single = state[2:3], SingleSequence(state=state, kr1=state[0:2], pos1=state[3:4], advance=state[1:4])
+            if not hooks and self._chain_ok(1) and V % 8 == 0:   # token selection (argmax or the draw) and step bookkeeping stay on the device
+                tok_buf = torch.zeros(max_new_tokens, device=dev, dtype=torch.int64)
+                tok_buf[0] = st.nxt[0]
+                st.on_device = od = OnDevice(x0=st.emb.index_select(0, st.nxt).contiguous(), tok_buf=tok_buf)
+                st.aws = self._decode_attn_workspace(dev, Vt.shape[4])
+                if sampling or proc or rec:
+                    od.logits = torch.empty((1, V), device=dev, dtype=torch.float32)
+                if not (sampling or proc):   # plain greedy: the lm_head launch leaves partial (max, argmax) pairs
+                    od.part_val, od.part_idx = torch.empty(V // 8, device=dev, dtype=torch.float32), torch.empty(V // 8, device=dev, dtype=torch.int32)
+        if hooks:
+            seq = self._generate_with_hooks(ids, st, first_logits, max_new, procs, criteria, streamer, eos, pad)
+            return self._generate_output(flags, seq, S0, rec, st.cache, lo)
+        od = st.on_device
+        toks = [st.nxt.clone()]
+        eos1 = eos[0] if eos else None   # the scalar route (one eos id, no stop string): token buffers compared on the host, no stop launch
+        if stop is not None:
+            closed = lambda t: stop["status"].tolist()[1] == 0   # the poll keeps its cadence: one small copy, {last step, rows still open}
+        else:
+            closed = lambda t: eos1 is not None and bool(((od.tok_buf[None, :t] if od is not None else torch.stack(toks, 1)) == eos1).any(1).all())
+        n_new = 1 + _run_steps(lambda: self._decode_step(st), max_new, use_graph, closed, after=None if od is not None else lambda: toks.append(st.nxt.clone()))
+        if stop is not None:   # the reference's shape and padding: up to the step at which the last row finished; later steps only touched slots beyond it
+            n_new = min(n_new, min(int(stop["stop_at"].max()), max_new) + 1)
+            new = stop["ids"][:, S0:S0 + n_new].to(torch.int64)
+        else:
+            new = od.tok_buf[None, :n_new].clone() if od is not None else torch.stack(toks, 1)
+            if eos1 is not None:  # everything after a row's first EOS becomes padding (GenerationMixin semantics)
+                after = (new == eos1).cumsum(1) - (new == eos1).long() > 0
+                new = torch.where(after, torch.full_like(new, pad), new)
+        return self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st.cache, lo)
+
+    @staticmethod
+    def _generate_output(flags, sequences, S0, rec, cache, lo):
+        """what generate() returns: the plain sequences, or under return_dict_in_generate the AfkGenerateOutput around them - n = generated columns, scores /
+        logits = the first n slots of the recorded buffers as tuples of [B, V] views, past_key_values = the cache of every token but the last"""
+        if not flags.return_dict:
+            return sequences
+        from .generation_output import AfkGenerateOutput
+        from .modeling import AfkKVCache
+
+        n = sequences.shape[1] - S0
+        rows = lambda k: tuple(rec[k][i] for i in range(n)) if rec and rec.get(k) is not None else None
+        logits = rows("logits")
+        scores = logits if (rec and rec.get("scores") is not None and rec["scores"] is rec.get("logits")) else rows("scores")   # the same tensor objects, as the reference
+        return AfkGenerateOutput(sequences=sequences, scores=scores, logits=logits, past_key_values=AfkKVCache(cache[0], cache[1], lo, S0 + n - 1))
+
+    def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits=False):
+        """GenerationMixin.compute_transition_scores (transformers/generation/utils.py:1433-1555) for greedy / sampled outputs: [B, len(scores)] fp32, the
+        score of every generated token (the last len(scores) columns of `sequences`) in `scores` - or `logits` - as generate(return_dict_in_generate=True)
+        returned them; normalize_logits: minus the row's logsumexp, i.e. log-probabilities (-inf entries, the tokens a processor or warper removed, count as
+        probability 0).  One launch (afk_transition_scores); tuples that are consecutive views of one buffer - what generate() returns - are read in place,
+        anything else is stacked first.  beam_indices: beam-search outputs are not produced by this implementation's generate() and are refused."""
+        if beam_indices is not None:
+            raise AfkError("compute_transition_scores(beam_indices=...) is not supported: generate() returns no beam-search outputs")
+        from .generation_output import step_buffer_view
+
+        scores = tuple(scores)
+        if not scores:
+            raise AfkError("compute_transition_scores: `scores` is empty")
+        if sequences.dim() != 2 or sequences.shape[1] < len(scores) or sequences.shape[0] != scores[0].shape[0]:
+            raise AfkError(f"compute_transition_scores: sequences {tuple(sequences.shape)} do not hold {len(scores)} generated columns for {scores[0].shape[0]} rows")
+        buf = step_buffer_view(scores) if scores[0].is_cuda else None
+        if buf is None:
+            buf = torch.stack([s.to(self.device_, torch.float32) for s in scores]).contiguous()
+        tokens = sequences[:, sequences.shape[1] - len(scores):].to(buf.device, torch.int64).contiguous()
+        return ops.transition_scores(buf, tokens, normalize=bool(normalize_logits))
+
+    @torch.no_grad()
+    def _generate_with_hooks(self, ids, st, logits, max_new, procs, criteria, streamer, eos, pad):
+        """GenerationMixin._sample's loop with its per-step callbacks (transformers/generation/utils.py:2730-2830): scores = logits_processor(input_ids,
+        logits); token = argmax / multinomial; finished rows emit pad; streamer.put(tokens) (the prompt first, streamer.end() at the end);
+        a row finishes on EOS or when stopping_criteria(input_ids, scores) says so.  Host code runs between the steps, so they are enqueued eagerly
+        (no HIP graph) - the decode kernels are the ones of the graph path, and a sampled token is draw t of afk_decode_sample on the PROCESSED scores (a
+        token a processor set to -inf is never drawn), the same draw the graph path makes for token t.  eos: the ids as a tuple, pad: decode_stop.resolve's."""
+        B = ids.shape[0]
+        dev = ids.device
+        eos = torch.tensor(eos, device=dev) if eos else None
+        pad = pad if pad is not None else 0
+        done = torch.zeros(B, device=dev, dtype=torch.bool)
+        stop = st.stop
+        seq = ids
+        if streamer is not None:
+            streamer.put(ids.cpu())
+        for t in range(max_new):
+            if t > 0:
+                logits = self._decode_logits(st)        # appends the K / V of st.nxt at the cache slot st.cur
+                (st.single.advance if st.single is not None else st.cur).add_(1)
+                self._record_and_process(st, logits, step_off=t)   # the built-in processors first: st.nxt is token t - 1 as appended to seq (pad for a finished row)
+                if procs:
+                    logits = procs(seq, logits)
+            # token 0 is drawn a second time here (generate() drew it for st.nxt): the same draw, the same scores row - which generate() has recorded where it is greedy
+            tok = self._pick_token(st, logits, step_off=t, record=t > 0)
+            tok = torch.where(done, torch.full_like(tok, pad), tok)
+            if stop is not None:   # the device rule (eos list, stop strings), eagerly and in front of the user's criteria; token 0 was judged by generate() - the same answer
+                tok = tok.contiguous()
+                _stop.apply(stop, tok, step_off=t, feed_pad=True)
+            seq = torch.cat([seq, tok[:, None]], dim=1)
+            if streamer is not None:
+                streamer.put(tok.cpu())
+            if stop is not None:
+                done = done | (stop["stop_at"] <= t)
+            elif eos is not None:
+                done = done | torch.isin(tok, eos)
+            if criteria:
+                r = criteria(seq, logits)
+                done = done | (r.to(dev).reshape(-1).bool() if torch.is_tensor(r) else torch.full_like(done, bool(r)))
+            if bool(done.all()):
+                break
+            st.nxt.copy_(tok)
+        if streamer is not None:
+            streamer.end()
+        return seq
+
+    @torch.no_grad()
+    def _generate_recompute(self, ids, input_features, input_features_mask, attention_mask, max_new_tokens, eos):
+        """reference path without a cache (every step re-runs the whole prefix through forward()): used by the tests to pin the cache path.  eos: a tuple"""
+        if ids.shape[0] != 1 and attention_mask is not None and not bool(attention_mask.all()):
+            raise AfkError("the recompute path does not support padded batches")
+        eos = torch.tensor(eos, device=ids.device) if eos else None
+        for _ in range(max_new_tokens):
+            out = self.forward(input_ids=ids, input_features=input_features, input_features_mask=input_features_mask, logits_to_keep=1)
+            nxt = out.logits[:, -1, :].float().argmax(-1, keepdim=True)
+            ids = torch.cat([ids, nxt], dim=1)
+            if eos is not None and bool(torch.isin(nxt, eos).all()):
+                break
+        return ids

@@ -21,22 +21,15 @@ Deviations from the oracle surface (documented, not silent):
   * ``AFK_EXACT_FP32=1`` routes the inference forward / greedy ``generate`` through the exact fp32 verification kernels (exact.py);
   * ``forward(use_cache=True)`` / ``forward(past_key_values=cache)``: the reference's cache protocol for inference (prefill returns an
     ``AfkKVCache``, later calls append one or several tokens); same kernels and cache layout as ``generate``;
-  * ``generate``: prefill fills a KV cache, each new token is one HIP-graph replay; greedy by default, ``do_sample=True`` with
-    ``temperature`` / ``top_k`` / ``top_p`` / ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff`` / ``seed`` (the reference's logits-warper order,
-    filtered and drawn on the device by one launch, ``afk_decode_sample_filtered``, inside the
-    replayed step: the ids are a function of the seed, not of torch's generator stream; top-p keeps a class of equal logits whole), or ``num_beams > 1`` (beam search with the
-    reference's scoring); ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens`` / ``suppress_tokens`` / ``begin_suppress_tokens`` are applied
-    on the device inside the replayed step (``afk_decode_process``, decode_process.py); ``generation_config`` supplies defaults;
-    ``return_dict_in_generate`` with ``output_scores`` / ``output_logits`` returns an ``AfkGenerateOutput`` (generation_output.py) whose per-step rows are kept from
-    inside the replayed step, and ``compute_transition_scores`` scores it; ``eos_token_id`` as a list and ``stop_strings=`` / ``tokenizer=`` are decided by
-    one launch inside the replayed step (``afk_decode_stop``, decode_stop.py); constrained / assisted decoding are not built;
+  * ``generate`` (generation.py, inherited as ``AfkGenerationMixin``): prefill fills a KV cache, each new token is one HIP-graph replay; greedy, sampled
+    or beam search, with the logits processors, the stopping rules and the output object decided by launches inside the replayed step - docs/generate.md
+    tells every route and what is not built (constrained / assisted decoding);
   * ``attention_mask`` rows must be one contiguous run of ones (left padding - the reference processor's default -, right padding, or
     both); masks with holes raise.  Hidden states of padded positions are zeros-attended garbage in both implementations and are
     never compared.
 """
 from __future__ import annotations
 
-import math
 import os
 from typing import Optional
 
@@ -44,11 +37,10 @@ import torch
 from torch import nn
 
 from . import _lib, ops
-from . import decode_process as _process
-from . import decode_stop as _stop
 from ._lib import AfkError
 from .arena import Arena
 from . import functional as F_
+from .generation import AfkGenerationMixin
 
 
 class AfkKVCache:
@@ -184,7 +176,7 @@ def _attach(root: nn.Module, name: str, param: nn.Parameter):
     m.register_parameter(parts[-1], param)
 
 
-class AudioFlamingo3ForConditionalGeneration(nn.Module):
+class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, nn.Module):
     """Drop-in for the oracle class of the same name (config = transformers.AudioFlamingo3Config or a duck-typed object)."""
 
     def __init__(self, config, device="cuda", init_seed: Optional[int] = 0):
@@ -817,6 +809,36 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
                 src = torch.where(src >= 0, row.to(torch.int32), src).contiguous()
         return ops.embed_scatter_fwd(ids_flat, src, a[lm + "embed_tokens.weight"].data, audio)
 
+    @staticmethod
+    def _pos_and_key_range(lo, start, n):
+        """n new positions per row at cache offset `start`, rows whose first real position is lo [B]: the rotary positions [B * n] (position_ids =
+        cumsum(mask) - 1) and the key range [lo, i + 1) of every query row [B, n, 2]"""
+        B = lo.shape[0]
+        ar = torch.arange(start, start + n, device=lo.device, dtype=torch.int32)
+        pos_rows = (ar[None, :] - lo[:, None]).clamp_min(0).reshape(-1).contiguous()
+        krange = torch.stack([lo[:, None].expand(B, n), torch.maximum(ar[None, :] + 1, lo[:, None])], -1).contiguous()
+        return pos_rows, krange
+
+    def _prefill_setup(self, attention_mask, B, n, headroom, who):
+        """what a prefill of n prompt positions per row into a FRESH cache needs (`who` names the caller in the error): lo [B] (the first real position of
+        every row: attention_mask may pad on the LEFT) and whether any row is padded, the zeroed cache Kc / Vt with `headroom` positions behind the prompt,
+        the rotary positions, the key ranges, and whether the LDS-staged causal kernels take the prompt"""
+        dev = self.device_
+        lo, padded = torch.zeros(B, device=dev, dtype=torch.int32), False
+        if attention_mask is not None:
+            am = attention_mask.to(dev)
+            if not bool(am.all()):
+                lens = am.sum(-1)
+                if not bool((am.flip(-1).cumsum(-1) == torch.minimum(torch.arange(1, n + 1, device=dev)[None], lens[:, None])).all()):
+                    raise AfkError(f"{who}: only LEFT-padded attention_mask is supported (pad the prompt on the left)")
+                lo, padded = (n - lens).to(torch.int32), True
+        Smax = n + headroom
+        Kc = torch.zeros((self.dec_layers, B, Smax, self.Hkv * self.D), device=dev, dtype=torch.bfloat16)
+        Vt = torch.zeros((self.dec_layers, B, self.Hkv, self.D, ops.pad64(Smax)), device=dev, dtype=torch.bfloat16)
+        pos_rows, krange = self._pos_and_key_range(lo, 0, n)
+        fast = self.D in (64, 128) and ops.ATTN_IMPL == "lds" and (self.left_pad_on_lds_kernels or not padded)
+        return lo, padded, Kc, Vt, pos_rows, krange, fast
+
     cache_headroom = 256  # forward(use_cache=True): positions reserved beyond the prompt; the cache grows by doubling when they run out
 
     @torch.no_grad()
@@ -839,22 +861,10 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             if past is not None and attention_mask is not None:
                 attention_mask = None    # consumed: the left padding is in past.lo, the new positions are all real
         if past is None:
-            lo = torch.zeros(B, device=dev, dtype=torch.int32)
-            padded = False
-            if attention_mask is not None:
-                am = attention_mask.to(dev)
-                if not bool(am.all()):
-                    lens = am.sum(-1)
-                    if not bool((am.flip(-1).cumsum(-1) == torch.minimum(torch.arange(1, n + 1, device=dev)[None], lens[:, None])).all()):
-                        raise AfkError("forward(use_cache=True): only LEFT-padded attention_mask is supported (pad the prompt on the left)")
-                    lo, padded = (n - lens).to(torch.int32), True
-            Smax = n + self.cache_headroom
-            Kc = torch.zeros((L, B, Smax, nk), device=dev, dtype=torch.bfloat16)
-            Vt = torch.zeros((L, B, self.Hkv, self.D, ops.pad64(Smax)), device=dev, dtype=torch.bfloat16)
+            lo, padded, Kc, Vt, pos_rows, krange, fast = self._prefill_setup(attention_mask, B, n, self.cache_headroom, "forward(use_cache=True)")
             if ids is not None:
                 x = self._merged_embeddings(ids, input_features, input_features_mask)
             start = 0
-            fast = self.D in (64, 128) and ops.ATTN_IMPL == "lds" and (self.left_pad_on_lds_kernels or not padded)
             kv_lo = lo if padded else None
         else:
             if not isinstance(past, AfkKVCache):
@@ -872,17 +882,14 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             if ids is not None:
                 x = ops.embed_scatter_fwd(ids.reshape(-1).contiguous(), None, self.arena[self._lm + "embed_tokens.weight"].data, None)
             fast, kv_lo = False, None
-        ar = torch.arange(start, start + n, device=dev, dtype=torch.int32)
+            pos_rows, krange = self._pos_and_key_range(lo, start, n)
         if position_ids is not None:
             # the rotary positions the caller computed (GenerationMixin: cumsum(attention_mask) - 1 of the whole sequence, sliced to the new tokens)
             pos_rows = position_ids.to(dev).expand(B, n).to(torch.int32).clamp_min(0).reshape(-1).contiguous()
         elif ref_cache is not None:
             # a reference cache and no position_ids: the reference rotates by cache_position = arange(past, past + n) whatever the mask says
             # (Qwen2Model.forward modeling_qwen2.py:361-364) - the keys already in the cache (or the reference's next call on it) follow that convention
-            pos_rows = ar[None, :].expand(B, n).reshape(-1).contiguous()
-        else:
-            pos_rows = (ar[None, :] - lo[:, None]).clamp_min(0).reshape(-1).contiguous()                   # position_ids = cumsum(mask) - 1
-        krange = torch.stack([lo[:, None].expand(B, n), torch.maximum(ar[None, :] + 1, lo[:, None])], -1).contiguous()   # [lo, i + 1)
+            pos_rows = torch.arange(start, start + n, device=dev, dtype=torch.int32)[None, :].expand(B, n).reshape(-1).contiguous()
         y = self._decode_layers(x, B, n, start, (Kc, Vt), pos_rows, krange, fast, kv_lo=kv_lo)
         keep = n if not logits_to_keep else min(int(logits_to_keep), n)
         rows = y.reshape(B, n, -1)[:, n - keep:, :].reshape(B * keep, -1).contiguous()
@@ -988,13 +995,12 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
 
     decode_chain = os.environ.get("AFK_DECODE_CHAIN", "1") == "1"   # single sequence: one launch per Linear (csrc/decode_chain.hip), five per layer
 
-    def _decode_layers_chain(self, x, cache, pos_rows, krange, start_dev, aws=None, head=None, greedy=None):
+    def _chain_layers(self, x, cache, pos_rows, krange, start_dev, aws=None):
         """one new position of ONE sequence: five launches per decoder layer (round 4; ten on the split-K + glue path above).  Every Linear is one
         weight-streaming launch in which a group of waves owns eight complete output rows: the qkv launch normalises the residual stream in its prologue
         and applies bias / RoPE / cache append in its epilogue, o_proj and down_proj add the residual, gate|up normalises in its prologue and multiplies
-        silu(gate) * up in its epilogue; the Q = 1 attention merges its key chunks in the last block to finish (afk_attn_decode_fused).  With `head`
-        (lm_head weight, rows % 8 == 0) the final RMSNorm + lm_head are one more launch of the same kind and the fp32 logits [1, V] come back; otherwise
-        the normalised hidden row."""
+        silu(gate) * up in its epilogue; the Q = 1 attention merges its key chunks in the last block to finish (afk_attn_decode_fused).  -> the residual row
+        behind the last layer, NOT through the final RMSNorm (_chain_lm_head takes it in its prologue)"""
         a, lm, Hq, Hkv, D = self.arena, self._lm, self.Hq, self.Hkv, self.D
         Kc, Vt = cache
         Smax, Spad = Kc.shape[2], Vt.shape[4]
@@ -1028,43 +1034,22 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             wd = A("mlp.down_proj.weight").data
             x = torch.empty_like(x2)
             _lib.call("afk_decode_chain_linear_residual", act.data_ptr(), wd.data_ptr(), wd.stride(0), H, I, x2.data_ptr(), x.data_ptr(), st)
-        if greedy is not None and (greedy.get("sampling") or greedy.get("proc")):
-            # sampled, or logits processors: the lm_head launch writes the fp32 logits; the processors' launch edits the row (and, greedy, selects from it and
-            # does the bookkeeping); the sample launch draws and does the bookkeeping
-            g = greedy
-            _lib.call("afk_decode_chain_lm_head", x.data_ptr(), a[lm + "norm.weight"].data.data_ptr(), eps, head.data_ptr(), head.stride(0), head.shape[0], H,
-                      g["logits"].data_ptr(), None, None, st)
-            rec = g.get("rec")
-            self._record_rows(rec, "logits", g["logits"], step_base=g["cur"], step_off=g["tok_off"])   # the raw row, in front of the processors
-            if g.get("proc"):
-                sel = {} if g.get("sampling") else dict(select=True, tokens_out=g["tok_buf"], tok_off=g["tok_off"], state=g["state"], emb=g["emb"], x_out=g["x0"])
-                _process.apply(g["proc"], g["logits"], next_token=g["nxt"], step_base=g["cur"], step_off=g["tok_off"], **sel)
-                if sel:
-                    # the selecting launch has advanced state[2] (= cur) itself, and the processed row it selected from is still in place: recorded BEHIND it,
-                    # one step further back (rather than inside the launch, which would put a vocabulary-sized store into afk_decode_process for this case only)
-                    self._record_rows(rec, "scores", g["logits"], step_base=g["cur"], step_off=g["tok_off"] - 1)
-                    return None
-            self._sample_token(g["logits"], g["sampling"], step_base=g["cur"], step_off=g["tok_off"], out=g["nxt"], tokens_out=g["tok_buf"], tok_off=g["tok_off"],
-                               state=g["state"], emb=g["emb"], x_out=g["x0"], **self._scores_kw(rec))
-            return None
-        if greedy is not None:   # generate()'s state dict: the lm_head launch leaves (max, argmax) per eight rows, the select launch does everything up to the next step
-            g = greedy
-            rec = g.get("rec")   # flags off: no logits row is written, as before; on: the same launch also leaves the row (the partial argmax pairs, hence the ids, are the same)
-            _lib.call("afk_decode_chain_lm_head", x.data_ptr(), a[lm + "norm.weight"].data.data_ptr(), eps, head.data_ptr(), head.stride(0), head.shape[0], H,
-                      g["logits"].data_ptr() if rec else None, g["part_val"].data_ptr(), g["part_idx"].data_ptr(), st)
-            if rec:   # no processor: scores and logits are the same rows (one buffer when both are asked for); in front of the select launch, which advances cur
-                self._record_rows(rec, "logits", g["logits"], step_base=g["cur"], step_off=g["tok_off"])
-                self._record_rows(rec, "scores", g["logits"], step_base=g["cur"], step_off=g["tok_off"])
-            _lib.call("afk_decode_select_greedy", g["part_val"].data_ptr(), g["part_idx"].data_ptr(), g["part_val"].numel(), g["nxt"].data_ptr(),
-                      g["tok_buf"].data_ptr(), g["tok_off"], g["state"].data_ptr(), g["emb"].data_ptr(), g["emb"].stride(0), H, g["x0"].data_ptr(), st)
-            return None
+        return x
+
+    def _chain_lm_head(self, x, head, logits=None, part_val=None, part_idx=None):
+        """the final RMSNorm + lm_head (rows % 8 == 0) on the residual row of _chain_layers, one more launch of the same kind: it leaves the fp32 logits [1, V]
+        and / or (max, argmax) per eight rows, whichever buffers are given"""
+        _lib.call("afk_decode_chain_lm_head", x.data_ptr(), self.arena[self._lm + "norm.weight"].data.data_ptr(), float(self.rms_eps), head.data_ptr(), head.stride(0),
+                  head.shape[0], x.shape[1], ops._p(logits), ops._p(part_val), ops._p(part_idx), ops._stream())
+
+    def _decode_layers_chain(self, x, cache, pos_rows, krange, start_dev, aws=None, head=None):
+        """_chain_layers, then with `head` (lm_head weight, rows % 8 == 0) the fp32 logits [1, V] of _chain_lm_head; otherwise the normalised hidden row"""
+        x = self._chain_layers(x, cache, pos_rows, krange, start_dev, aws=aws)
         if head is not None:
-            logits = torch.empty((1, head.shape[0]), device=dev, dtype=torch.float32)
-            _lib.call("afk_decode_chain_lm_head", x.data_ptr(), a[lm + "norm.weight"].data.data_ptr(), eps, head.data_ptr(), head.stride(0), head.shape[0], H,
-                      logits.data_ptr(), None, None, st)
+            logits = torch.empty((1, head.shape[0]), device=x.device, dtype=torch.float32)
+            self._chain_lm_head(x, head, logits=logits)
             return logits
-        y, _ = ops.rmsnorm_fwd(x, a[lm + "norm.weight"].data, self.rms_eps)
-        return y
+        return ops.rmsnorm_fwd(x, self.arena[self._lm + "norm.weight"].data, self.rms_eps)[0]
 
     decode_mfma_from = int(os.environ.get("AFK_DECODE_MFMA_FROM", "2"))   # batched decode: sequences per step from which the norm-in-prologue matrix-pipe launches run
     last_layer_rows_only = os.environ.get("AFK_LAST_LAYER_ROWS", "1") == "1"   # training forward with labels: the last decoder layer behind its attention on the labelled rows only
@@ -1207,570 +1192,31 @@ class AudioFlamingo3ForConditionalGeneration(nn.Module):
             raise AfkError(f"decode attention: workspace of {aws.numel()} floats for {ns} splits over spad {spad} (needs {need}): allocate it for this cache")
         return ns
 
-    def _decode_step(self, st):
-        """one greedy or sampled decode step on static buffers (everything position-dependent lives on the device): HIP-graph capturable"""
-        if "x0" in st:   # one sequence: 5 launches per layer + lm_head + ONE launch for argmax or the draw / token / positions / the next embedding row
-            self._decode_layers_chain(st["x0"], st["cache"], st["pos1"], st["kr1"], st["cur"], aws=st["aws"], head=st["head"], greedy=st)
-            if st.get("stop"):   # behind the selection launch, which has advanced cur (= state[2]) already: one step back.  The next embedding row is in x0: no pad is fed
-                _stop.apply(st["stop"], st["nxt"], step_base=st["cur"], step_off=st["tok_off"] - 1)
-            return
-        logits = self._decode_logits(st)
-        rec = st.get("rec")
-        self._record_rows(rec, "logits", logits, step_base=st["cur"], step_off=st["tok_off"])
-        if st.get("proc"):   # the token being generated is number cur + 1 - S0: the processors' (and the draw's) counter lives on the device and advances with the step
-            _process.apply(st["proc"], logits, next_token=st["nxt"], step_base=st["cur"], step_off=st["tok_off"])
-        if st.get("sampling"):
-            self._sample_token(logits, st["sampling"], step_base=st["cur"], step_off=st["tok_off"], out=st["nxt"], **self._scores_kw(rec))
-        else:
-            self._record_rows(rec, "scores", logits, step_base=st["cur"], step_off=st["tok_off"])
-            st["nxt"].copy_(self._select_token(logits))
-        if st.get("stop"):   # the stopping rule on the token just selected; a row that finished earlier emits pad_token_id and the next step embeds it
-            _stop.apply(st["stop"], st["nxt"], step_base=st["cur"], step_off=st["tok_off"], feed_pad=True)
-        (st["advance"] if "advance" in st else st["cur"]).add_(1)   # single sequence: cur, position and the key-range end live in one tensor (generate())
-
-    @torch.no_grad()
-    def _beam_search(self, ids, last_hidden, cache, lo, nb, max_new, eos_token_id, pad_token_id, length_penalty, early_stopping, *, num_return=1,
-                     use_graph=None):
-        """Beam search on the KV cache with GenerationMixin's scoring (transformers/generation/utils.py:3008-3400): every batch row keeps `nb`
-        running beams ranked by accumulated log-probability; at each step the best (n_eos + 1) * nb continuations over all beams are drawn, the
-        ones among the top nb that end (EOS, or the length limit) compete for the row's nb FINISHED slots with score = sum / generated_length ^
-        length_penalty, the best nb that do not end continue.  The loop stops when no running beam can still beat the worst finished one
-        (the reference's heuristic: best running sum / current generated length ^ length_penalty; early_stopping = True: as soon as every
-        finished slot is filled; "never": the optimistic bound at the maximum length when length_penalty > 0) or the length limit is reached.
-        The KV cache is reordered by beam parentage every step.  Returns the best num_return finished hypotheses per row as [B * num_return, S0 + longest],
-        padded with pad_token_id (eos if none).
-        Two routes with identical results.  On the device (beam_on_device, inside the caps of afk_beam_step, AFK_EXACT_FP32 off): _beam_search_device - the
-        step is one afk_beam_step and one afk_beam_reorder_cache behind the forward pass, captured and replayed under the use_graph rule of generate().
-        Otherwise the host loop below: torch ops over [B, nb * V], one host synchronisation and one index_select copy of the whole cache per token."""
-        from . import exact as _exact
-
-        dev = self.device_
-        B, S0 = ids.shape
-        Kc, Vt = cache
-        V = self.V
-        eos = [] if eos_token_id is None else ([int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple)) else [int(eos_token_id)])
-        if self.beam_on_device and not _exact.ENABLED and ops.beam_caps_ok(nb, len(eos), V):
-            return self._beam_search_device(ids, last_hidden, cache, lo, nb, max_new, eos, pad_token_id, length_penalty, early_stopping, num_return, use_graph)
-        keep = (len(eos) + 1) * nb
-        rep = torch.arange(B, device=dev).repeat_interleave(nb)
-        Kc, Vt = Kc.index_select(1, rep).contiguous(), Vt.index_select(1, rep).contiguous()
-        st = {"cache": (Kc, Vt), "lo": lo.index_select(0, rep).contiguous(), "head": self.arena["lm_head.weight"].data,
-              "emb": self.arena[self._lm + "embed_tokens.weight"].data, "cur": torch.full((1,), S0, device=dev, dtype=torch.int32),
-              "nxt": torch.zeros(B * nb, device=dev, dtype=torch.int64)}
-        run_seq = torch.zeros((B, nb, max_new), device=dev, dtype=torch.int64)
-        run_score = torch.full((B, nb), -1.0e9, device=dev, dtype=torch.float32)
-        run_score[:, 0] = 0.0                                           # all beams of a row start identical: only the first one is live
-        fin_seq = torch.zeros((B, nb, max_new), device=dev, dtype=torch.int64)
-        fin_len = torch.zeros((B, nb), device=dev, dtype=torch.int64)
-        fin_score = torch.full((B, nb), -1.0e9, device=dev, dtype=torch.float32)
-        fin_done = torch.zeros((B, nb), device=dev, dtype=torch.bool)
-        logits = ops.gemm_nt(last_hidden, st["head"]).float().index_select(0, rep)      # next-token logits after the prompt, one copy per beam
-        top_mask = torch.arange(keep, device=dev) < nb
-        boff = (torch.arange(B, device=dev) * nb)[:, None]
-        can_improve = torch.ones((B, 1), device=dev, dtype=torch.bool)
-        for t in range(max_new):
-            logp = torch.log_softmax(logits, dim=-1).view(B, nb, V) + run_score[:, :, None]
-            cand_score, cand = logp.view(B, nb * V).topk(keep, dim=-1)
-            parent, tok = cand // V, cand % V
-            cand_seq = run_seq.gather(1, parent[:, :, None].expand(B, keep, max_new)).clone()
-            cand_seq[:, :, t] = tok
-            ends = torch.zeros_like(tok, dtype=torch.bool)
-            for e in eos:
-                ends |= tok == e
-            if t + 1 == max_new:
-                ends[:] = True                                            # the length limit finishes whatever is left
-            # finished slots: candidates among the top nb that end, scored sum / generated_length ^ length_penalty
-            fscore = cand_score / float((t + 1) ** length_penalty)
-            full = fin_done.all(-1, keepdim=True) & (early_stopping is True)
-            fscore = fscore + (full | ~can_improve | ~(ends & top_mask[None])).float() * -1.0e9
-            ms, mi = torch.cat([fin_score, fscore], 1).topk(nb, dim=-1)
-            fin_seq = torch.cat([fin_seq, cand_seq], 1).gather(1, mi[:, :, None].expand(B, nb, max_new))
-            fin_len = torch.cat([fin_len, torch.full_like(tok, t + 1)], 1).gather(1, mi)
-            fin_done = torch.cat([fin_done, ends & top_mask[None]], 1).gather(1, mi)
-            fin_score = ms
-            # running beams: the best nb candidates that do not end
-            rs, ri = (cand_score + ends.float() * -1.0e9).topk(nb, dim=-1)
-            run_seq, run_score = cand_seq.gather(1, ri[:, :, None].expand(B, nb, max_new)), rs
-            if t + 1 == max_new:
-                break
-            # can a running beam still beat the worst finished hypothesis?  (reference heuristic, utils.py:3008-3052)
-            hyp_len = (max_new if (early_stopping == "never" and length_penalty > 0.0) else (t + 1))
-            best_running = run_score[:, :1] / float(hyp_len ** length_penalty)
-            worst_fin = torch.where(fin_done, fin_score.min(-1, keepdim=True).values, torch.full_like(fin_score, -1.0e9))
-            can_improve = can_improve & (best_running > worst_fin).any(-1, keepdim=True)
-            if not bool(can_improve.any()) or (early_stopping is True and bool(fin_done.all())):
-                break
-            # advance the model: reorder the cache by parentage, feed the chosen tokens
-            src = (parent.gather(1, ri) + boff).reshape(-1)
-            Kc.copy_(Kc.index_select(1, src)), Vt.copy_(Vt.index_select(1, src))
-            st["nxt"].copy_(tok.gather(1, ri).reshape(-1))
-            logits = self._decode_logits(st)
-            st["cur"].add_(1)
-        return self._beam_result(ids, fin_seq, fin_len, num_return, pad_token_id, eos)
-
-    @staticmethod
-    def _beam_result(ids, fin_seq, fin_len, n, pad_token_id, eos):
-        """the best n finished hypotheses of every row (fin_seq [B, nb, max_new], fin_len [B, nb], in ranking order) behind the prompt: [B * n, S0 + longest],
-        row b * n + k = hypothesis k of row b, padded with pad_token_id (the first eos id if none, 0 without one) - the reference's order and shape"""
-        B, _, max_new = fin_seq.shape
-        best_seq, best_len = fin_seq[:, :n].reshape(B * n, max_new), fin_len[:, :n].reshape(B * n)
-        pad = pad_token_id if pad_token_id is not None else (eos[0] if eos else 0)
-        best_seq = torch.where(torch.arange(max_new, device=best_seq.device)[None] < best_len[:, None], best_seq, torch.full_like(best_seq, pad))
-        return torch.cat([ids.repeat_interleave(n, dim=0) if n > 1 else ids, best_seq[:, : int(best_len.max())]], dim=1)
-
-    beam_on_device = os.environ.get("AFK_BEAM_DEVICE", "1") == "1"   # beam search: the step's decisions and the cache move as launches of the decode step (csrc/decode_beam.hip)
-
-    @torch.no_grad()
-    def _beam_search_device(self, ids, last_hidden, cache, lo, nb, max_new, eos, pad_token_id, length_penalty, early_stopping, num_return, use_graph):
-        """_beam_search with every per-token decision on the device.  A step is _decode_logits -> afk_beam_step (log-softmax, the row's top (n_eos + 1) * nb
-        continuations, finished slots, running beams, the early-stop heuristic, {t, open} in a status word) -> afk_beam_reorder_cache (the slots written since
-        the prompt move by parentage, in place: the beams of a row share their prompt keys bit for bit) -> cur += 1; nothing in it depends on the host, so it is
-        captured at t == 2 and replayed.  Token 0 runs eagerly with the kernel of the captured steps.  The host polls the status word every 8th step (steps
-        behind the closing one write nothing) and reads the finished hypotheses back once."""
-        dev = self.device_
-        B, S0 = ids.shape
-        Kc, Vt = cache
-        rep = torch.arange(B, device=dev).repeat_interleave(nb)
-        Kc, Vt = Kc.index_select(1, rep).contiguous(), Vt.index_select(1, rep).contiguous()
-        bs = ops.beam_state(B, nb, max_new, device=dev, eos=eos, length_penalty=length_penalty, early_stopping=early_stopping)
-        st = {"cache": (Kc, Vt), "lo": lo.index_select(0, rep).contiguous(), "head": self.arena["lm_head.weight"].data,
-              "emb": self.arena[self._lm + "embed_tokens.weight"].data, "cur": torch.full((1,), S0, device=dev, dtype=torch.int32), "nxt": bs["next_token"]}
-        ops.beam_step(ops.gemm_nt(last_hidden, st["head"]).float().index_select(0, rep).contiguous(), bs, step_off=0)
-
-        def step():   # token t = cur + 1 - S0: the forward pass appends the keys of token t - 1 at slot cur, so the slots S0 .. cur move
-            logits = self._decode_logits(st)
-            ops.beam_step(logits if logits.is_contiguous() else logits.contiguous(), bs, step_base=st["cur"], step_off=1 - S0)
-            ops.beam_reorder_cache(Kc, Vt, bs["src"], st["cur"], nb=nb, S0=S0, max_new=max_new)
-            st["cur"].add_(1)
-
-        if use_graph is None:
-            use_graph = max_new > 3
-        graph = None
-        for t in range(1, max_new):
-            if t % 8 == 0 and bs["status"].tolist()[1] == 0:   # one small copy, {last step, open}
-                break
-            if use_graph and t == 2:   # step 1 ran eagerly (lazy one-time initialisation inside the library happens outside the capture)
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    step()
-                graph.replay()
-            elif graph is not None:
-                graph.replay()
-            else:
-                step()
-        fin_seq, fin_len, _, _ = ops.beam_finished(bs)
-        return self._beam_result(ids, fin_seq, fin_len, num_return, pad_token_id, eos)
-
     def _decode_logits(self, st):
-        """logits [B, V] (fp32) of the position after st["nxt"]: one pass over the decoder weights, cache append at st["cur"] (not advanced here)"""
-        B = st["nxt"].shape[0]
-        x = st["emb"].index_select(0, st["nxt"])
-        if "pos1" in st:   # single sequence (generate()): views of the step-state tensor, advanced by ONE add per step
-            pos1, kr1 = st["pos1"], st["kr1"]
+        """logits [B, V] (fp32) of the position after st.nxt (a generation.DecodeState): one pass over the decoder weights, cache append at st.cur (not advanced here)"""
+        B = st.nxt.shape[0]
+        x = st.emb.index_select(0, st.nxt)
+        if st.single is not None:   # single sequence (generate()): views of the step-state tensor, advanced by ONE add per step
+            pos1, kr1 = st.single.pos1, st.single.kr1
         else:
-            pos1 = (st["cur"] - st["lo"]).contiguous()
-            kr1 = torch.stack([st["lo"], (st["cur"] + 1).expand(B)], -1).reshape(B, 1, 2).contiguous()
-        if (self._chain_ok(1) and 2 <= B <= self._chain_batch_cap(st["head"]) and st["head"].shape[0] % 8 == 0 and self.I % 4 == 0):
-            if "aws" not in st:
-                st["aws"] = self._decode_attn_workspace(x.device, st["cache"][1].shape[4], B)
-            return self._decode_layers_chain_batched(x.contiguous(), B, st["cache"], pos1, kr1, st["cur"], st["aws"], st["head"])
+            pos1 = (st.cur - st.lo).contiguous()
+            kr1 = torch.stack([st.lo, (st.cur + 1).expand(B)], -1).reshape(B, 1, 2).contiguous()
+        if (self._chain_ok(1) and 2 <= B <= self._chain_batch_cap(st.head) and st.head.shape[0] % 8 == 0 and self.I % 4 == 0):
+            if st.aws is None:
+                st.aws = self._decode_attn_workspace(x.device, st.cache[1].shape[4], B)
+            return self._decode_layers_chain_batched(x.contiguous(), B, st.cache, pos1, kr1, st.cur, st.aws, st.head)
         if self._chain_ok(B):
-            if "aws" not in st:
-                st["aws"] = self._decode_attn_workspace(x.device, st["cache"][1].shape[4])
-            head = st["head"] if st["head"].shape[0] % 8 == 0 else None
-            y = self._decode_layers_chain(x.contiguous(), st["cache"], pos1, kr1, st["cur"], aws=st["aws"], head=head)
+            if st.aws is None:
+                st.aws = self._decode_attn_workspace(x.device, st.cache[1].shape[4])
+            head = st.head if st.head.shape[0] % 8 == 0 else None
+            y = self._decode_layers_chain(x.contiguous(), st.cache, pos1, kr1, st.cur, aws=st.aws, head=head)
             if head is not None:
                 return y
         elif self.decode_fused_glue and B <= ops.GEMV_MAX_M and self.D in (64, 128) and self.decode_splits > 0 and ops.SPLITK:
-            y = self._decode_layers_fused(x.contiguous(), B, st["cache"], pos1, kr1, st["cur"])
+            y = self._decode_layers_fused(x.contiguous(), B, st.cache, pos1, kr1, st.cur)
         else:
-            y = self._decode_layers(x, B, 1, None, st["cache"], pos1, kr1, False, start_dev=st["cur"])
-        return ops.gemm_nt(y, st["head"]).float()
-
-    @staticmethod
-    def _select_token(logits, sampling=None):
-        """greedy argmax, or GenerationMixin's sampling chain on the [B, V] fp32 logits of the new position: temperature -> top-k -> top-p
-        (TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper, transformers/generation/logits_process.py) -> softmax -> multinomial.
-        Token selection is O(B*V) index work outside the training hot path: plain torch ops."""
-        if not sampling:
-            return logits.argmax(-1)
-        t, k, p_, gen = sampling["temperature"], sampling["top_k"], sampling["top_p"], sampling["generator"]
-        if t and t != 1.0:
-            logits = logits / t
-        if k and k > 0:
-            kth = logits.topk(min(k, logits.shape[-1]), -1).values[..., -1:]
-            logits = logits.masked_fill(logits < kth, float("-inf"))
-        if p_ is not None and p_ < 1.0:
-            sl, si = logits.sort(-1, descending=False)
-            drop = sl.softmax(-1).cumsum(-1) <= (1.0 - p_)
-            drop[..., -1:] = False  # always keep the most likely token
-            logits = logits.masked_fill(drop.scatter(-1, si, drop), float("-inf"))
-        return torch.multinomial(logits.softmax(-1), 1, generator=gen).squeeze(-1)
-
-    @staticmethod
-    def _record_rows(rec, which, rows, *, step_base=None, step_off=0):
-        """generate(output_logits / output_scores): one afk_decode_record launch that keeps the fp32 rows [B, V] in slot *step_base + step_off of rec[which]
-        ([max_new_tokens, B, V]).  Nothing is enqueued when the buffer was not asked for, or when `scores` shares the buffer of `logits` (greedy decoding with
-        no processor: the row is recorded once, under "logits")."""
-        if not rec or rec.get(which) is None or (which == "scores" and rec.get("logits") is rec["scores"]):
-            return
-        if rows.dtype != torch.float32 or rows.stride(-1) != 1:   # only what a user logits_processor returned (token 0 and the eager hook loop): the captured
-            rows = rows.float().contiguous()                      # steps hand over the fp32 rows the lm_head wrote, so nothing is allocated or copied there
-        ops.decode_record(rows, rec[which], step_base=step_base, step_off=step_off)
-
-    @staticmethod
-    def _scores_kw(rec):
-        """the sampler's keywords that make its launch keep the warped row (afk_decode_sample_scored); {} when scores were not asked for"""
-        return dict(scores_out=rec["scores"]) if rec and rec.get("scores") is not None else {}
-
-    @staticmethod
-    def _sample_token(logits, sampling, **kw):
-        """the sampling chain of _select_token on the device, in one launch and with no host state (ops.decode_sample): temperature -> top-k -> top-p ->
-        min_p -> typical_p -> epsilon_cutoff -> eta_cutoff -> the draw from a counter-based generator keyed by sampling["seed"]; kw: the draw's counter
-        (step_base / step_off) and the outputs.  Every sampled token of generate() - the first, the batched step, the one-sequence chain, the hook loop - comes
-        through here with the same `sampling` dict."""
-        if logits.dtype != torch.float32 or logits.stride(-1) != 1:
-            logits = logits.float().contiguous()
-        return ops.decode_sample(logits, temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"], seed=sampling["seed"],
-                                 min_p=sampling["min_p"], typical_p=sampling["typical_p"], epsilon_cutoff=sampling["epsilon_cutoff"],
-                                 eta_cutoff=sampling["eta_cutoff"], **kw)
-
-    @torch.no_grad()
-    def generate(self, input_ids, input_features=None, input_features_mask=None, attention_mask=None, max_new_tokens=20,
-                 do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, eos_token_id=None, pad_token_id=None, use_cache=True,
-                 use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, repetition_penalty=1.0,
-                 no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, min_p=None, typical_p=1.0,
-                 epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, **kwargs):
-        """Greedy decoding, sampling or beam search (GenerationMixin.generate, transformers/generation/utils.py; do_sample with temperature /
-        top_k / top_p / min_p / typical_p / epsilon_cutoff / eta_cutoff as its logits warpers apply them and in their order, drawn on the device by afk_decode_sample from a counter-based generator: seed (64 bits; None: from
-        torch.seed()) and the index of the token are all the state there is, so a seed gives the same ids in eager, graph-replayed and hook-driven loops; num_beams > 1: beam search with the
-        reference's scoring - accumulated log-probabilities, finished hypotheses ranked by sum / length^length_penalty, its early-stop
-        heuristic).  generation_config (a transformers.GenerationConfig or anything with the same attributes) supplies defaults for the
-        arguments left at theirs, as GenerationMixin merges them.
-        repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens: the logits processors
-        GenerationMixin._get_logits_processor puts in front of the warpers, with its validation (decode_process.resolve), applied in its order by ONE launch per
-        step (afk_decode_process) on a device-resident id history - the prompt ids as passed, padding and <sound> ids included, then every selected token - so
-        greedy and sampled steps still replay in the decode graph; user `logits_processor`s run after them, as the reference appends them.  With none of them
-        active nothing extra is enqueued.  They are refused with num_beams > 1 and with use_cache=False.  Not covered (refused as keywords, ignored in a
-        generation config as before): bad_words_ids (its reference class adds a bias to the whole row and handles multi-token sequences; single ids are what
-        suppress_tokens does); top_h (its warper sits in front of top-k and is a sequential scan); forced_eos_token_id,
-        encoder_*, sequence_bias, exponential_decay_length_penalty.
-        min_p / typical_p / epsilon_cutoff / eta_cutoff run inside the sampler's launch behind top-p (afk_decode_sample_filtered), so a sampled step with them still
-        replays in the decode graph.  Gating and validation are the reference's (decode_process.resolve_warpers): min_p outside [0, 1] and typical_p <= 0 raise
-        ValueError, typical_p >= 1 and epsilon_cutoff / eta_cutoff outside (0, 1) are inactive, and do_sample=False ignores all four.  Left at their defaults they
-        are taken from the generation config like top_p - a config that carries one of them was ignored before and now changes the distribution sampled from, as
-        it does in the reference.
-        return_dict_in_generate / output_scores / output_logits (keyword first, else the generation config: GenerationMixin's rule, utils.py:2829-2837):
-        with return_dict_in_generate the call returns an AfkGenerateOutput (generation_output.py: GenerateDecoderOnlyOutput's fields and access surface) -
-        `sequences`, exactly the tensor the same call returns without the flags; `logits` / `scores`, tuples of n = sequences.shape[1] - S0 tensors [B, V] fp32:
-        the raw lm_head rows, and the rows after the built-in processors, any user logits_processor and - sampled - the warpers (logits / temperature on the
-        kept set, -inf elsewhere); `past_key_values`, the AfkKVCache of every token but the last, which forward(past_key_values=...) takes as is.  The rows are
-        kept from inside the captured step - one afk_decode_record launch per kind and step, none for sampled scores, which the sampler's launch writes itself
-        (afk_decode_sample_scored) - into ONE buffer per kind allocated up front: max_new_tokens x B x V x 4 bytes each, 608 KB per row and step at the AF3
-        vocabulary (a 256-token, 8-row call with both kinds holds 2.5 GB); the tuples are views of it.  Greedy decoding with no processor returns the same
-        views under both names (the reference returns the same tensors).  output_scores / output_logits without return_dict_in_generate collect nothing and
-        return the plain tensor, silently, as the reference does.  A generation config that sets return_dict_in_generate=True was ignored before and now
-        returns the object - and raises where it also asks for one of the refused combinations below, as a config with output_attentions / output_hidden_states
-        now does.  With the flags off nothing extra is enqueued.  do_sample=True
-        with top_k=1 stays the greedy shortcut it is (routing it through the sampler could move ids on tied bf16 logits): its `scores` are the processed,
-        un-warped rows.  Refused, by an AfkError that names the combination: the output object with num_beams > 1 (the reference returns another class, with
-        beam_indices), with use_cache=False or with AFK_EXACT_FP32=1; output_attentions / output_hidden_states.  compute_transition_scores() scores the result.
-        Stopping.  eos_token_id: an int, list, tuple or tensor (keyword, else the generation config - Qwen2.5 ships [151645, 151643]); pad_token_id defaults to
-        the first eos id; stop_strings= (a string or a list; keyword, else the generation config) needs tokenizer= and raises the reference's ValueError without
-        one (decode_stop.resolve).  With MORE THAN ONE eos id, or with stop strings, the rule is ONE launch of the step (afk_decode_stop; decode_stop.py): it
-        appends the token just selected to a device-resident id buffer - the prompt ids as passed, then the emitted tokens -, judges the row (EosTokenCriteria;
-        StopStringCriteria over the table that class computes: it is constructed on the host and its table uploaded once), records the step at which the row
-        finished, and for a row that finished earlier emits pad_token_id and - in the batched step - feeds it to the next step, as the reference does.  Greedy
-        and sampled steps with it still replay in the decode graph; the loop polls a two-word status every 8th step, and the result is cut at the step at which
-        the last row finished: the reference's shape and padding, which `scores`, `logits` and `past_key_values` follow, and the `scores` / `logits` of a
-        batched row behind its stop are the rows the reference computes.  The hook loop (below) runs the same launch eagerly, in front of the user's
-        stopping_criteria.  With a SINGLE eos id and no stop string - a list holding one id included - generate() enqueues exactly what it did before this
-        route existed and returns what it returned: the loop compares token buffers on the host every 8th step, so the length is rounded up to that poll
-        (everything behind a row's first EOS is pad_token_id), and a batched row keeps feeding the token it selected after its own EOS, so there the entries
-        of `scores` / `logits` of a row behind its first EOS are unspecified.  Unifying the two routes is a follow-up.  Refused, by an AfkError that names the
-        combination: stop strings with num_beams > 1, with use_cache=False or with AFK_EXACT_FP32=1; tokenizer= when no stop string is active.  Not covered:
-        max_time, ConfidenceCriteria, user criteria objects inside the graph.
-        Beam search (num_beams > 1) runs in the decode graph like the other modes: a step is the forward pass, afk_beam_step - the fp32 log-softmax of every
-        beam plus its running score, the row's best (n_eos + 1) * num_beams continuations, the finished slots ranked by sum / length ** length_penalty, the
-        running beams, the early-stop heuristic (early_stopping False / True / "never") and a status word - and afk_beam_reorder_cache, which moves the cache
-        slots written since the prompt by beam parentage, in place (the beams of a row share their prompt keys bit for bit, so nothing else has to move and no
-        second cache is allocated).  The step is captured under the use_graph rule, the loop polls the status word every 8th step and reads the finished
-        hypotheses back once.  Where torch.topk leaves the order of EQUAL scores open this route fixes it: the lower flat index beam * V + token first.
-        Outside the kernel's caps (2 <= num_beams <= 16, (n_eos + 1) * num_beams <= 64), with AFK_EXACT_FP32=1 or with AFK_BEAM_DEVICE=0 (the class attribute
-        beam_on_device) the same search runs as a host loop of torch ops, with the same results (tests/test_beam_gpu.py).
-        num_return_sequences (keyword, else the generation config; GenerationConfig.validate's rules and messages): with beams, the best n finished
-        hypotheses of every row as [B * n, S0 + longest], row b * n + k = hypothesis k of row b, padded with pad_token_id - n > num_beams raises ValueError;
-        with do_sample, ids, features, masks and attention_mask are repeated row by row before the prefill (GenerationMixin._expand_inputs_for_generation) and
-        the draw, keyed by (step, row), makes the copies differ; greedy decoding with n > 1 raises ValueError.  Out of scope for beams, and refused as before:
-        the output object, beam_indices in compute_transition_scores and per-step beam scores; the logits processors, stop strings and hooks; beam sampling
-        (do_sample with num_beams > 1).  Follow-ups: a prefill shared between sampled copies (prefill kernels choose tiles by row count, so it would not be
-        bit-equal to the expanded call), and sharing the prompt keys between the beams of a row inside the attention kernel.
-        Cache handling as
-        Qwen2Attention.forward modeling_qwen2.py:213-214).  Prefill runs the prompt once and fills a per-layer KV cache; every new
-        token then costs one pass over the weights and one Q=1 attention over the cache.  Batches may be LEFT padded
-        (attention_mask, as the processor pads): positions count real tokens only and padded keys are never visible.
-        The decode step is launch-bound in eager mode (~370 small launches per token), so it is captured once into a HIP graph and
-        replayed (use_graph=None: whenever more than 3 tokens are requested)."""
-        self._require_hip()
-        procs, criteria, streamer = kwargs.pop("logits_processor", None), kwargs.pop("stopping_criteria", None), kwargs.pop("streamer", None)
-        out_kw = {k: kwargs.pop(k, None) for k in ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")}
-        stop_strings, tokenizer = kwargs.pop("stop_strings", None), kwargs.pop("tokenizer", None) or None
-        for k in ("synced_gpus", "use_model_defaults", "assistant_model"):
-            if kwargs.get(k):
-                raise AfkError(f"generate({k}=...) is not supported by this implementation")
-            kwargs.pop(k, None)
-        if kwargs:
-            raise AfkError(f"generate(): unknown / unsupported arguments {sorted(kwargs)}")
-        hooks = bool(procs) or bool(criteria) or streamer is not None   # GenerationMixin's per-step callbacks: host code between the steps -> eager steps
-        gc = generation_config if generation_config is not None else getattr(self, "generation_config", None)
-        if gc is not None:  # explicit arguments win; anything still at its default is taken from the generation config
-            pick = lambda cur, default, name: getattr(gc, name, None) if (cur == default and getattr(gc, name, None) is not None) else cur
-            max_new_tokens = pick(max_new_tokens, 20, "max_new_tokens")
-            do_sample, temperature, top_k, top_p = pick(do_sample, False, "do_sample"), pick(temperature, 1.0, "temperature"), pick(top_k, 50, "top_k"), pick(top_p, 1.0, "top_p")
-            num_beams, length_penalty, early_stopping = pick(num_beams, 1, "num_beams"), pick(length_penalty, 1.0, "length_penalty"), pick(early_stopping, False, "early_stopping")
-            eos_token_id, pad_token_id = pick(eos_token_id, None, "eos_token_id"), pick(pad_token_id, None, "pad_token_id")
-        spec = _process.resolve(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, begin_suppress_tokens, eos_token_id=eos_token_id,
-                                generation_config=gc)   # the five logits processors: keyword, else generation config, validated as the reference does
-        from . import exact as _exact
-        from . import generation_output as _gout
-
-        # the stopping rule: the eos ids as a tuple, pad defaulted to the first of them, stop strings (keyword, else generation config) with their refusals
-        stop_spec = _stop.resolve(eos_token_id, pad_token_id, stop_strings, tokenizer, generation_config=gc, num_beams=int(num_beams), use_cache=bool(use_cache),
-                                  exact_fp32=_exact.ENABLED)
-        if len(stop_spec.eos) == 1:
-            eos_token_id = stop_spec.eos[0]         # a list holding one id is the scalar case
-        elif stop_spec.eos:
-            eos_token_id = list(stop_spec.eos)      # beam search, the exact path and the hook loop take lists; the graph / eager loop takes the device route
-
-        n_ret = _gout.resolve_num_return_sequences(num_return_sequences, generation_config=gc, num_beams=int(num_beams), do_sample=bool(do_sample))
-        flags = _gout.resolve_output_flags(**out_kw, generation_config=gc, num_beams=int(num_beams), use_cache=bool(use_cache), exact_fp32=_exact.ENABLED)
-        if int(max_new_tokens) <= 0:   # GenerationMixin refuses it as well (generation/configuration_utils.py validate())
-            raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
-        if spec.active and (num_beams > 1 or not use_cache):
-            raise AfkError("generate(repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens): greedy or sampled "
-                           "decoding on the KV cache only (no num_beams > 1, no use_cache=False)")
-        if _exact.ENABLED and not do_sample and num_beams == 1 and not hooks and not spec.active and type(self).__name__ == "AudioFlamingo3ForConditionalGeneration":
-            # AFK_EXACT_FP32=1: greedy decoding by exact-fp32 recomputation of the prefix (exact.py) - the reference's greedy ids with no "confident rows" filter
-            return _exact.greedy_generate(self, input_ids, input_features, input_features_mask, attention_mask, max_new_tokens, eos_token_id, pad_token_id)
-        if num_beams > 1 and (do_sample or not use_cache):
-            raise AfkError("generate(num_beams > 1): beam search is deterministic and runs on the KV cache (no do_sample, no use_cache=False)")
-        if hooks and (num_beams > 1 or not use_cache):
-            raise AfkError("generate(logits_processor / stopping_criteria / streamer): greedy or sampled decoding on the KV cache only")
-        sampling = None
-        warp = _process.resolve_warpers(min_p, typical_p, epsilon_cutoff, eta_cutoff, generation_config=gc, do_sample=bool(do_sample) and num_beams == 1)
-        if do_sample and int(top_k or 0) != 1:   # top_k == 1 is greedy selection (and keeps the no-logits path)
-            sampling = dict(temperature=float(temperature) if temperature else 1.0, top_k=int(top_k or 0), top_p=1.0 if top_p is None else float(top_p),
-                            seed=(int(seed) if seed is not None else int(torch.seed())) & (2 ** 64 - 1), **warp)
-        ids = input_ids.to(self.device_)
-        if n_ret > 1 and int(num_beams) == 1:   # sampled copies: GenerationMixin._expand_inputs_for_generation - every tensor input repeated row by row; the
-            expand = lambda x: x.repeat_interleave(n_ret, dim=0) if torch.is_tensor(x) else x   # draw is keyed by (step, row), so the copies differ
-            ids, input_features, input_features_mask, attention_mask = expand(ids), expand(input_features), expand(input_features_mask), expand(attention_mask)
-        if not use_cache:
-            if do_sample:
-                raise AfkError("generate(use_cache=False) is the greedy reference path of the tests")
-            return self._generate_recompute(ids, input_features, input_features_mask, attention_mask, max_new_tokens, eos_token_id)
-        B, S0 = ids.shape
-        dev = self.device_
-        lo = torch.zeros(B, device=dev, dtype=torch.int32)
-        padded = False
-        if attention_mask is not None:
-            am = attention_mask.to(dev)
-            if not bool(am.all()):
-                padded = True
-                lens = am.sum(-1)
-                if not bool((am.flip(-1).cumsum(-1) == torch.minimum(torch.arange(1, S0 + 1, device=dev)[None], lens[:, None])).all()):
-                    raise AfkError("generate(): only LEFT-padded attention_mask is supported (pad the prompt on the left)")
-                lo = (S0 - lens).to(torch.int32)
-        Smax = S0 + max_new_tokens
-        L, nk = self.dec_layers, self.Hkv * self.D
-        Kc = torch.zeros((L, B, Smax, nk), device=dev, dtype=torch.bfloat16)
-        Vt = torch.zeros((L, B, self.Hkv, self.D, ops.pad64(Smax)), device=dev, dtype=torch.bfloat16)
-        ar = torch.arange(S0, device=dev, dtype=torch.int32)
-        pos_rows = (ar[None, :] - lo[:, None]).clamp_min(0).reshape(-1).contiguous()          # position_ids = cumsum(mask) - 1
-        krange = torch.stack([lo[:, None].expand(B, S0), torch.maximum(ar[None, :] + 1, lo[:, None])], -1).contiguous()  # [lo, i+1)
-        x = self._merged_embeddings(ids, input_features, input_features_mask)
-        fast = self.D in (64, 128) and ops.ATTN_IMPL == "lds" and (self.left_pad_on_lds_kernels or not padded)
-        y = self._decode_layers(x, B, S0, 0, (Kc, Vt), pos_rows, krange, fast, kv_lo=lo if padded else None)
-        last = y.reshape(B, S0, -1)[:, -1, :].contiguous()
-        if num_beams > 1:
-            return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), int(max_new_tokens), eos_token_id, pad_token_id, float(length_penalty), early_stopping,
-                                     num_return=n_ret, use_graph=use_graph)
-        first_logits = ops.gemm_nt(last, self.arena["lm_head.weight"].data).float()
-        rec = None
-        if flags.collect:   # one [max_new_tokens, B, V] fp32 buffer per kind, allocated once: static memory the captured step writes a slot of
-            new_buf = lambda: torch.empty((int(max_new_tokens), B, first_logits.shape[1]), device=dev, dtype=torch.float32)
-            rec = {"logits": new_buf() if flags.logits else None, "scores": None}
-            if flags.scores:   # greedy with no processor of any kind: the reference returns the same tensors in both tuples - one buffer, one record per step
-                rec["scores"] = rec["logits"] if (flags.logits and not sampling and not spec.active and not procs) else new_buf()
-            self._record_rows(rec, "logits", first_logits, step_off=0)   # token 0, eagerly, with the kernel of the captured steps
-        proc = None
-        if spec.active:   # token 0, eagerly, with the kernel of the captured steps; in front of the user's processors (GenerationMixin._merge_criteria_processor_list)
-            proc = _process.build_state(spec, ids, int(max_new_tokens), first_logits.shape[1])
-            _process.apply(proc, first_logits)
-        if procs:
-            first_logits = procs(ids, first_logits)
-        if not sampling:
-            self._record_rows(rec, "scores", first_logits, step_off=0)
-        st = {"cache": (Kc, Vt), "lo": lo, "head": self.arena["lm_head.weight"].data, "emb": self.arena[self._lm + "embed_tokens.weight"].data,
-              "cur": torch.full((1,), S0, device=dev, dtype=torch.int32), "sampling": sampling, "tok_off": 1 - S0, "proc": proc, "rec": rec,
-              "nxt": self._sample_token(first_logits, sampling, **self._scores_kw(rec)) if sampling else self._select_token(first_logits)}   # the first token is draw 0
-        stop = None
-        if stop_spec.device:   # more than one eos id, or stop strings: the rule is a launch of the step.  Token 0, eagerly, with the kernel of the captured steps
-            stop = _stop.build_state(stop_spec, ids, int(max_new_tokens), _stop.build_table(tokenizer, stop_spec.stop_strings) if stop_spec.stop_strings else None)
-            _stop.apply(stop, st["nxt"], step_off=0)
-        st["stop"] = stop
-        if B == 1:   # one device tensor [lo, key-range end, cache slot, position] -> the views the kernels read; one add per step moves the last three
-            state = torch.cat([lo, torch.tensor([S0 + 1, S0], device=dev, dtype=torch.int32), S0 - lo]).contiguous()
-            st.update(cur=state[2:3], kr1=state[0:2], pos1=state[3:4], advance=state[1:4], state=state)
-            if not hooks and self._chain_ok(1) and st["head"].shape[0] % 8 == 0:   # token selection (argmax or the draw) and step bookkeeping stay on the device
-                tok_buf = torch.zeros(max_new_tokens, device=dev, dtype=torch.int64)
-                tok_buf[0] = st["nxt"][0]
-                st.update(x0=st["emb"].index_select(0, st["nxt"]).contiguous(), aws=self._decode_attn_workspace(dev, Vt.shape[4]), tok_buf=tok_buf)
-                if sampling or proc or rec:
-                    st.update(logits=torch.empty((1, st["head"].shape[0]), device=dev, dtype=torch.float32))
-                if not (sampling or proc):
-                    st.update(part_val=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.float32),
-                              part_idx=torch.empty(st["head"].shape[0] // 8, device=dev, dtype=torch.int32))
-        if hooks:
-            seq = self._generate_with_hooks(ids, st, first_logits, int(max_new_tokens), procs, criteria, streamer, eos_token_id, stop_spec.pad)
-            return self._generate_output(flags, seq, S0, rec, st["cache"], lo)
-        on_device = "x0" in st
-        n_new = 1
-        toks = [st["nxt"].clone()]
-        if use_graph is None:
-            use_graph = max_new_tokens > 3
-        graph = None
-        for t in range(1, max_new_tokens):
-            if stop is not None:
-                if t % 8 == 0 and stop["status"].tolist()[1] == 0:   # the poll keeps its cadence: one small copy, {last step, rows still open}
-                    break
-            elif eos_token_id is not None and t % 8 == 0 and bool(((st["tok_buf"][None, :t] if on_device else torch.stack(toks, 1)) == eos_token_id).any(1).all()):
-                break
-            if use_graph and t == 2:  # step 1 ran eagerly (lazy one-time initialisation inside the library happens outside the capture)
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    self._decode_step(st)
-                graph.replay()  # capture only records: the step for t == 2 itself still has to run
-            elif graph is not None:
-                graph.replay()
-            else:
-                self._decode_step(st)
-            if not on_device:
-                toks.append(st["nxt"].clone())
-            n_new = t + 1
-        if stop is not None:   # the reference's shape and padding: up to the step at which the last row finished; later steps only touched slots beyond it
-            n_new = min(n_new, min(int(stop["stop_at"].max()), int(max_new_tokens)) + 1)
-            new = stop["ids"][:, S0:S0 + n_new].to(torch.int64)
-            return self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st["cache"], lo)
-        new = st["tok_buf"][None, :n_new].clone() if on_device else torch.stack(toks, 1)
-        if eos_token_id is not None:  # everything after a row's first EOS becomes padding (GenerationMixin semantics)
-            after = (new == eos_token_id).cumsum(1) - (new == eos_token_id).long() > 0
-            new = torch.where(after, torch.full_like(new, pad_token_id if pad_token_id is not None else eos_token_id), new)
-        return self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st["cache"], lo)
-
-    @staticmethod
-    def _generate_output(flags, sequences, S0, rec, cache, lo):
-        """what generate() returns: the plain sequences, or under return_dict_in_generate the AfkGenerateOutput around them - n = generated columns, scores /
-        logits = the first n slots of the recorded buffers as tuples of [B, V] views, past_key_values = the cache of every token but the last"""
-        if not flags.return_dict:
-            return sequences
-        from .generation_output import AfkGenerateOutput
-
-        n = sequences.shape[1] - S0
-        rows = lambda k: tuple(rec[k][i] for i in range(n)) if rec and rec.get(k) is not None else None
-        logits = rows("logits")
-        scores = logits if (rec and rec.get("scores") is not None and rec["scores"] is rec.get("logits")) else rows("scores")   # the same tensor objects, as the reference
-        return AfkGenerateOutput(sequences=sequences, scores=scores, logits=logits, past_key_values=AfkKVCache(cache[0], cache[1], lo, S0 + n - 1))
-
-    def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits=False):
-        """GenerationMixin.compute_transition_scores (transformers/generation/utils.py:1433-1555) for greedy / sampled outputs: [B, len(scores)] fp32, the
-        score of every generated token (the last len(scores) columns of `sequences`) in `scores` - or `logits` - as generate(return_dict_in_generate=True)
-        returned them; normalize_logits: minus the row's logsumexp, i.e. log-probabilities (-inf entries, the tokens a processor or warper removed, count as
-        probability 0).  One launch (afk_transition_scores); tuples that are consecutive views of one buffer - what generate() returns - are read in place,
-        anything else is stacked first.  beam_indices: beam-search outputs are not produced by this implementation's generate() and are refused."""
-        if beam_indices is not None:
-            raise AfkError("compute_transition_scores(beam_indices=...) is not supported: generate() returns no beam-search outputs")
-        from .generation_output import step_buffer_view
-
-        scores = tuple(scores)
-        if not scores:
-            raise AfkError("compute_transition_scores: `scores` is empty")
-        if sequences.dim() != 2 or sequences.shape[1] < len(scores) or sequences.shape[0] != scores[0].shape[0]:
-            raise AfkError(f"compute_transition_scores: sequences {tuple(sequences.shape)} do not hold {len(scores)} generated columns for {scores[0].shape[0]} rows")
-        buf = step_buffer_view(scores) if scores[0].is_cuda else None
-        if buf is None:
-            buf = torch.stack([s.to(self.device_, torch.float32) for s in scores]).contiguous()
-        tokens = sequences[:, sequences.shape[1] - len(scores):].to(buf.device, torch.int64).contiguous()
-        return ops.transition_scores(buf, tokens, normalize=bool(normalize_logits))
-
-    @torch.no_grad()
-    def _generate_with_hooks(self, ids, st, logits, max_new, procs, criteria, streamer, eos_token_id, pad_token_id):
-        """GenerationMixin._sample's loop with its per-step callbacks (transformers/generation/utils.py:2730-2830): scores = logits_processor(input_ids,
-        logits); token = argmax / multinomial; finished rows emit pad_token_id; streamer.put(tokens) (the prompt first, streamer.end() at the end);
-        a row finishes on EOS or when stopping_criteria(input_ids, scores) says so.  Host code runs between the steps, so they are enqueued eagerly
-        (no HIP graph) - the decode kernels are the ones of the graph path, and a sampled token is draw t of afk_decode_sample on the PROCESSED scores (a
-        token a processor set to -inf is never drawn), the same draw the graph path makes for token t."""
-        B = ids.shape[0]
-        dev = ids.device
-        eos = None if eos_token_id is None else torch.as_tensor(eos_token_id, device=dev).reshape(-1)
-        pad = pad_token_id if pad_token_id is not None else (int(eos[0]) if eos is not None else 0)
-        done = torch.zeros(B, device=dev, dtype=torch.bool)
-        stop = st.get("stop")
-        seq = ids
-        if streamer is not None:
-            streamer.put(ids.cpu())
-        for t in range(max_new):
-            if t > 0:
-                logits = self._decode_logits(st)        # appends the K / V of st["nxt"] at the cache slot st["cur"]
-                (st["advance"] if "advance" in st else st["cur"]).add_(1)
-                self._record_rows(st.get("rec"), "logits", logits, step_off=t)
-                if st.get("proc"):   # the built-in processors first: st["nxt"] is token t - 1 as appended to seq (pad for a finished row)
-                    _process.apply(st["proc"], logits, next_token=st["nxt"], step_off=t)
-                if procs:
-                    logits = procs(seq, logits)
-            if st.get("sampling"):   # token 0 is drawn a second time here (generate() drew it for st["nxt"]): the same draw, the same scores row
-                tok = self._sample_token(logits, st["sampling"], step_off=t, **self._scores_kw(st.get("rec")))
-            else:
-                if t > 0:
-                    self._record_rows(st.get("rec"), "scores", logits, step_off=t)
-                tok = self._select_token(logits)
-            tok = torch.where(done, torch.full_like(tok, pad), tok)
-            if stop is not None:   # the device rule (eos list, stop strings), eagerly and in front of the user's criteria; token 0 was judged by generate() - the same answer
-                tok = tok.contiguous()
-                _stop.apply(stop, tok, step_off=t, feed_pad=True)
-            seq = torch.cat([seq, tok[:, None]], dim=1)
-            if streamer is not None:
-                streamer.put(tok.cpu())
-            if stop is not None:
-                done = done | (stop["stop_at"] <= t)
-            elif eos is not None:
-                done = done | torch.isin(tok, eos)
-            if criteria:
-                r = criteria(seq, logits)
-                done = done | (r.to(dev).reshape(-1).bool() if torch.is_tensor(r) else torch.full_like(done, bool(r)))
-            if bool(done.all()):
-                break
-            st["nxt"].copy_(tok)
-        if streamer is not None:
-            streamer.end()
-        return seq
-
-    @torch.no_grad()
-    def _generate_recompute(self, ids, input_features, input_features_mask, attention_mask, max_new_tokens, eos_token_id):
-        """reference path without a cache (every step re-runs the whole prefix through forward()): used by the tests to pin the cache path"""
-        if ids.shape[0] != 1 and attention_mask is not None and not bool(attention_mask.all()):
-            raise AfkError("the recompute path does not support padded batches")
-        for _ in range(max_new_tokens):
-            out = self.forward(input_ids=ids, input_features=input_features, input_features_mask=input_features_mask,
-                               logits_to_keep=1)
-            nxt = out.logits[:, -1, :].float().argmax(-1, keepdim=True)
-            ids = torch.cat([ids, nxt], dim=1)
-            if eos_token_id is not None and bool(torch.isin(nxt, torch.as_tensor(eos_token_id, device=nxt.device)).all() if isinstance(eos_token_id, list)
-                                                 else (nxt == eos_token_id).all()):
-                break
-        return ids
+            y = self._decode_layers(x, B, 1, None, st.cache, pos1, kr1, False, start_dev=st.cur)
+        return ops.gemm_nt(y, st.head).float()
 
     # gradient bookkeeping -------------------------------------------------------------------------
     def zero_grad(self, set_to_none: bool = False):

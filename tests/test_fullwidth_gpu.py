@@ -153,6 +153,7 @@ def test_fullwidth_decode_step_vs_recompute(dev, B, monkeypatch):
     training-path kernels (which test_fullwidth_depth_reduced_model_vs_oracle pins to the oracle).  Tolerance: LOGIT_TOL of test_model_gpu (4e-2 at logit scale ~1)."""
     import bench
     from audio_flamingo_amd import _lib
+    from audio_flamingo_amd.generation import DecodeState
     from audio_flamingo_amd.modeling import AudioFlamingo3ForConditionalGeneration as Mine
 
     m = Mine(bench.af3_7b_config(enc_layers=1, dec_layers=1), device=dev, init_seed=5)
@@ -172,8 +173,8 @@ def test_fullwidth_decode_step_vs_recompute(dev, B, monkeypatch):
         nxt = pre.logits[:, -1].float().argmax(-1)
         ref = m(input_ids=torch.cat([ids, nxt[:, None]], 1), logits_to_keep=1).logits[:, -1].float()
         c = pre.past_key_values
-        st = {"cache": (c.K, c.Vt), "lo": c.lo, "head": m.arena["lm_head.weight"].data, "emb": m.arena[m._lm + "embed_tokens.weight"].data,
-              "cur": torch.full((1,), int(c.length), device=dev, dtype=torch.int32), "nxt": nxt, "sampling": None}
+        st = DecodeState(cache=(c.K, c.Vt), lo=c.lo, head=m.arena["lm_head.weight"].data, emb=m.arena[m._lm + "embed_tokens.weight"].data,
+                         cur=torch.full((1,), int(c.length), device=dev, dtype=torch.int32), nxt=nxt, sampling=None)
         called = []
         real = _lib.call
         monkeypatch.setattr(_lib, "call", lambda name, *a: (called.append(name), real(name, *a))[1])
@@ -181,7 +182,7 @@ def test_fullwidth_decode_step_vs_recompute(dev, B, monkeypatch):
         got = {}
         for chain in (True, False):
             m.decode_chain = chain
-            st.pop("aws", None)
+            st.aws = None
             del called[:]
             got[chain] = m._decode_logits(st).float()
             torch.cuda.synchronize()
