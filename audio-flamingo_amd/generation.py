@@ -312,7 +312,8 @@ class AfkGenerationMixin:
                  do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, eos_token_id=None, pad_token_id=None, use_cache=True,
                  use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, min_p=None, typical_p=1.0,
-                 epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, **kwargs):
+                 epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, sequence_bias=None, bad_words_ids=None, min_length=0,
+                 forced_eos_token_id=None, exponential_decay_length_penalty=None, **kwargs):
         """Greedy decoding, sampling or beam search on a KV cache, with GenerationMixin.generate's arguments and results; docs/generate.md describes every
         route, what it launches and how it differs from the reference.
 
@@ -322,7 +323,10 @@ class AfkGenerationMixin:
         do_sample (False) with temperature (1.0) / top_k (50; 1 is greedy) / top_p (1.0) / min_p / typical_p (1.0) / epsilon_cutoff (0.0) / eta_cutoff (0.0)
         and seed (None: from torch.seed()): one seed gives the same ids on every route.
         num_beams (1) with length_penalty (1.0) / early_stopping (False, True, "never"); num_return_sequences (1; needs beams or do_sample).
-        repetition_penalty (1.0) / no_repeat_ngram_size (0) / min_new_tokens (0) / suppress_tokens / begin_suppress_tokens: the built-in logits processors.
+        sequence_bias / repetition_penalty (1.0) / no_repeat_ngram_size (0) / bad_words_ids / min_length (0) / min_new_tokens (0) / forced_eos_token_id /
+        exponential_decay_length_penalty / suppress_tokens / begin_suppress_tokens: the built-in logits processors, applied in this order (the reference's) by
+        one launch per token, in front of logits_processor= and the warpers.  Not built: renormalize_logits, remove_invalid_values, encoder_*, top_h,
+        prefix_allowed_tokens_fn (decode_process.py says why).
         eos_token_id (int, list, tuple or tensor) / pad_token_id (default: the first eos id) / stop_strings= with tokenizer=.
         logits_processor= / stopping_criteria= / streamer=: the reference's per-step hooks; with one of them the steps run eagerly.
         return_dict_in_generate= with output_scores= / output_logits=: an AfkGenerateOutput (sequences, scores, logits, past_key_values) in place of the ids.
@@ -353,8 +357,10 @@ class AfkGenerationMixin:
             do_sample, temperature, top_k, top_p = pick(do_sample, False, "do_sample"), pick(temperature, 1.0, "temperature"), pick(top_k, 50, "top_k"), pick(top_p, 1.0, "top_p")
             num_beams, length_penalty, early_stopping = pick(num_beams, 1, "num_beams"), pick(length_penalty, 1.0, "length_penalty"), pick(early_stopping, False, "early_stopping")
             eos_token_id, pad_token_id = pick(eos_token_id, None, "eos_token_id"), pick(pad_token_id, None, "pad_token_id")
+        # the ten built-in logits processors: keyword, else generation config, validated as the reference does
         spec = _process.resolve(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, begin_suppress_tokens, eos_token_id=eos_token_id,
-                                generation_config=gc)   # the five logits processors: keyword, else generation config, validated as the reference does
+                                generation_config=gc, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, min_length=min_length,
+                                forced_eos_token_id=forced_eos_token_id, exponential_decay_length_penalty=exponential_decay_length_penalty)
         from . import exact as _exact
         from . import generation_output as _gout
 
@@ -368,8 +374,9 @@ class AfkGenerationMixin:
         if int(max_new_tokens) <= 0:   # GenerationMixin refuses it as well (generation/configuration_utils.py validate())
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         if spec.active and (num_beams > 1 or not use_cache):
-            raise AfkError("generate(repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens): greedy or sampled "
-                           "decoding on the KV cache only (no num_beams > 1, no use_cache=False)")
+            raise AfkError("generate(repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens / sequence_bias / "
+                           "bad_words_ids / min_length / forced_eos_token_id / exponential_decay_length_penalty): greedy or sampled decoding on the KV cache "
+                           "only (no num_beams > 1, no use_cache=False)")
         if _exact.ENABLED and not do_sample and num_beams == 1 and not hooks and not spec.active and type(self).__name__ == "AudioFlamingo3ForConditionalGeneration":
             # AFK_EXACT_FP32=1: greedy decoding by exact-fp32 recomputation of the prefix (exact.py) - the reference's greedy ids with no "confident rows" filter
             return _exact.greedy_generate(self, input_ids, input_features, input_features_mask, attention_mask, max_new_tokens, list(eos) or None, pad)

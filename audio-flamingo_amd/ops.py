@@ -836,6 +836,14 @@ def decode_process(logits, hist, seen, *, S0, penalty=1.0, ngram=0, suppress=Non
     one bit per vocabulary id of the row's history (decode_process.build_state fills both from the prompt); next_token [B] int64: the token selected for t - 1,
     appended by the launch (only token 0 has none).  suppress / begin_suppress / eos: int32 id lists on the device.  select (B == 1; state, emb, x_out, and
     tokens_out / tok_off): greedy selection from the processed row and the step bookkeeping of afk_decode_select_greedy in the same launch.  -> logits"""
+    _lib.call("afk_decode_process", *_decode_process_args(logits, hist, seen, S0, penalty, ngram, suppress, begin_suppress, eos, min_new_tokens, next_token,
+                                                          step_base, step_off, select, tokens_out, tok_off, state, emb, x_out), _stream())
+    return logits
+
+
+def _decode_process_args(logits, hist, seen, S0, penalty, ngram, suppress, begin_suppress, eos, min_new_tokens, next_token, step_base, step_off, select,
+                         tokens_out, tok_off, state, emb, x_out):
+    """the checks of decode_process / decode_process_ex -> the 29 arguments their entry points share"""
     _chk(logits, torch.float32, "decode_process logits")
     if logits.dim() != 2 or logits.stride(1) != 1:
         raise AfkError(f"decode_process logits: [B, V] with unit column stride, got {tuple(logits.shape)} strides {logits.stride()}")
@@ -862,11 +870,50 @@ def decode_process(logits, hist, seen, *, S0, penalty=1.0, ngram=0, suppress=Non
         if x_out.numel() < H or not x_out.is_contiguous() or V > emb.shape[0]:
             raise AfkError(f"decode_process: x_out holds {x_out.numel()} elements, emb is {tuple(emb.shape)} for V = {V}")
     n_of = lambda t_: 0 if t_ is None else t_.numel()
-    _lib.call("afk_decode_process", logits.data_ptr(), logits.stride(0), B, V, hist.data_ptr(), hist.stride(0), int(S0), seen.data_ptr(), seen.stride(0),
-              _p(step_base), int(step_off), _p(next_token), float(penalty), int(ngram), _p(suppress) if n_of(suppress) else None, n_of(suppress),
-              _p(begin_suppress) if n_of(begin_suppress) else None, n_of(begin_suppress), _p(eos) if n_of(eos) else None, n_of(eos), int(min_new_tokens),
-              1 if select else 0, _p(tokens_out) if select else None, int(tok_off), _p(state) if select else None, _p(emb) if select else None,
-              emb.stride(0) if select else 0, H, _p(x_out) if select else None, _stream())
+    return (logits.data_ptr(), logits.stride(0), B, V, hist.data_ptr(), hist.stride(0), int(S0), seen.data_ptr(), seen.stride(0),
+            _p(step_base), int(step_off), _p(next_token), float(penalty), int(ngram), _p(suppress) if n_of(suppress) else None, n_of(suppress),
+            _p(begin_suppress) if n_of(begin_suppress) else None, n_of(begin_suppress), _p(eos) if n_of(eos) else None, n_of(eos), int(min_new_tokens),
+            1 if select else 0, _p(tokens_out) if select else None, int(tok_off), _p(state) if select else None, _p(emb) if select else None,
+            emb.stride(0) if select else 0, H, _p(x_out) if select else None)
+
+
+def _sequence_table_args(tb, name, dev):
+    """a packed sequence table (decode_process.pack_sequences, as device tensors; None = empty) -> its 8 arguments, the shapes checked against each other: the
+    kernel trusts the offsets"""
+    if tb is None:
+        return (None, None, None, 0, None, None, None, 0)
+    for k, dt in (("ids", torch.int32), ("seq_off", torch.int32), ("seq_bias", torch.float32), ("group_id", torch.int32), ("group_l1", torch.float32),
+                  ("group_off", torch.int32)):
+        _chk(tb[k], dt, f"decode_process_ex {name}.{k}")
+        if tb[k].dim() != 1 or not tb[k].is_contiguous() or tb[k].device != dev:
+            raise AfkError(f"decode_process_ex {name}.{k}: a contiguous 1-d tensor on {dev}, got {tuple(tb[k].shape)} on {tb[k].device}")
+    n_seqs, n_groups = tb["seq_bias"].numel(), tb["group_id"].numel()
+    if n_groups < 1 or tb["group_l1"].numel() != n_groups or tb["group_off"].numel() != n_groups + 1 or tb["seq_off"].numel() != n_seqs + 1:
+        raise AfkError(f"decode_process_ex {name}: {n_groups} groups (>= 1) need group_l1 [{n_groups}], group_off [{n_groups + 1}]; {n_seqs} sequences need "
+                       f"seq_off [{n_seqs + 1}]")
+    return (_p(tb["ids"]) if tb["ids"].numel() else None, _p(tb["seq_off"]), _p(tb["seq_bias"]) if n_seqs else None, n_seqs, _p(tb["group_id"]),
+            _p(tb["group_l1"]), _p(tb["group_off"]), n_groups)
+
+
+def decode_process_ex(logits, hist, seen, *, S0, max_new_tokens, bias=None, bad=None, min_length=0, forced_eos=None, decay=None, decay_start=0, penalty=1.0,
+                      ngram=0, suppress=None, begin_suppress=None, eos=None, min_new_tokens=0, next_token=None, step_base=None, step_off=0, select=False,
+                      tokens_out=None, tok_off=0, state=None, emb=None, x_out=None):
+    """decode_process with the other built-in processors in the reference's order, still one launch (afk_decode_process_ex; the contract is in include/afk.h):
+    sequence bias -> repetition penalty -> no-repeat n-gram -> bad words -> min_length / min_new_tokens -> forced EOS at token max_new_tokens - 1 -> exponential
+    decay length penalty -> suppress / begin-suppress.  bias / bad: packed sequence tables as dicts of device tensors (decode_process.pack_sequences, which
+    refuses ids outside the vocabulary; bad's biases are -inf); forced_eos: int32 id list; decay: fp32 [>= max_new_tokens], decay[t] = pow(factor, t -
+    decay_start) - 1, applied to the eos ids when t > decay_start.  The offsets inside a table are trusted: build it with pack_sequences.  -> logits"""
+    common = _decode_process_args(logits, hist, seen, S0, penalty, ngram, suppress, begin_suppress, eos, min_new_tokens, next_token, step_base, step_off,
+                                  select, tokens_out, tok_off, state, emb, x_out)
+    for t_, dt, name in ((forced_eos, torch.int32, "forced_eos"), (decay, torch.float32, "decay")):
+        if t_ is not None:
+            _chk(t_, dt, f"decode_process_ex {name}")
+            if t_.dim() != 1 or not t_.is_contiguous():
+                raise AfkError(f"decode_process_ex {name}: a contiguous 1-d tensor, got {tuple(t_.shape)}")
+    n_of = lambda t_: 0 if t_ is None else t_.numel()
+    _lib.call("afk_decode_process_ex", *common, *_sequence_table_args(bias, "bias", logits.device), *_sequence_table_args(bad, "bad", logits.device),
+              int(min_length), _p(forced_eos) if n_of(forced_eos) else None, n_of(forced_eos), _p(decay), n_of(decay), int(decay_start), int(max_new_tokens),
+              _stream())
     return logits
 
 

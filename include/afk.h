@@ -460,6 +460,38 @@ int afk_decode_process(float* logits, int64_t ld_logits, int B, int V, int* hist
                        const int* step_base, int step_off, int64_t* next_token, float penalty, int no_repeat_ngram_size, const int* suppress, int n_suppress,
                        const int* begin_suppress, int n_begin_suppress, const int* eos, int n_eos, int min_new_tokens, int select, int64_t* tokens_out,
                        int tok_off, int* state, const void* emb, int64_t ld_emb, int H, void* x_out, void* stream);
+/* afk_decode_process with the other built-in processors of GenerationMixin._get_logits_processor (transformers/generation/utils.py:1154-1290) in their places -
+ * SequenceBiasLogitsProcessor, NoBadWordsLogitsProcessor, MinLengthLogitsProcessor, ForcedEOSTokenLogitsProcessor, ExponentialDecayLengthPenalty
+ * (transformers/generation/logits_process.py) - still ONE launch, one block per row, no host state: enqueue-only, no allocation, capturable.  The first 29
+ * arguments, step 0, the selection block and the rules for t, hist and seen are afk_decode_process's.  cur_len = n = S0 + t.  Per row, in this order:
+ *   1. sequence_bias (:1288-1319), n_bias_groups > 0: for every id, acc = 0.0f + l1[id]; then for every sequence of length L >= 2 that ends in id, in the table's
+ *      order, acc += (L <= n and the last L - 1 ids of the history equal the sequence's first L - 1) ? bias : 0.0f; then x = x + acc on EVERY entry of the row - one
+ *      fp32 add, so a -0.0 logit becomes +0.0 and -inf + (+inf) is NaN.  The order of the fp32 sum is the table's: one thread walks one group, no atomics.
+ *   2. repetition penalty (step 1 of afk_decode_process), on the row the bias left.
+ *   3. no-repeat n-gram (step 2 of afk_decode_process).
+ *   4. bad_words_ids (:1450-1467), n_bad_groups > 0: step 1 of this list with a second table whose biases are -inf, on the row steps 2 and 3 left.
+ *   5. min_length (:155-161): logits[id] = -inf for the eos ids when n < min_length.
+ *   6. min_new_tokens: logits[id] = -inf for the eos ids when t < min_new_tokens.
+ *   7. forced EOS (:1648-1654), n_forced_eos > 0 and t == max_new_tokens - 1: the whole row becomes -inf, then the forced_eos ids become 0.0.
+ *   8. exponential decay length penalty (:1765-1776), decay != null, n_eos > 0 and t > decay_start: x[id] = x[id] + |x[id]| * decay[t] for every eos id ONCE
+ *      (IEEE fp32 multiply, then add: no fused multiply-add), |x[id]| read from the row steps 1-7 left, and x = x + 0.0f on every other entry.  decay[t] =
+ *      float32(pow(factor, t - start) - 1) computed by the caller in double; a t past the table reads its last entry.
+ *   9. logits[id] = -inf for the suppress ids always and the begin_suppress ids when t == 0.
+ * A sequence table is packed by the caller, grouped by last id in a stable order: group g stands for the id group_id[g], l1 = group_l1[g] (the bias of the one-id
+ * sequence, 0.0f where there is none) and the sequences group_off[g] .. group_off[g + 1) of length >= 2; sequence s has the bias seq_bias[s] and, in front of its
+ * last id, the ids[seq_off[s] .. seq_off[s + 1]).  Every id of the vocabulary is in at most one group.  No cap on the number or the length of sequences.  The one
+ * eos list serves steps 5, 6 and 8.  Group ids outside [0, V) are skipped and the other ids of a table are only compared, so a table cannot make the launch write
+ * outside the row; the caller refuses such ids when it packs the table (the reference raises on them).  Refused here: a table, forced_eos or decay with a count
+ * and a null pointer, max_new_tokens < 1, min_length < 0, and a decay table of fewer than max_new_tokens entries.  With n_bias_groups == n_bad_groups ==
+ * min_length == n_forced_eos == 0 and decay == null the row is afk_decode_process's, bit for bit. */
+int afk_decode_process_ex(float* logits, int64_t ld_logits, int B, int V, int* hist, int64_t ld_hist, int S0, unsigned int* seen, int64_t ld_seen,
+                          const int* step_base, int step_off, int64_t* next_token, float penalty, int no_repeat_ngram_size, const int* suppress, int n_suppress,
+                          const int* begin_suppress, int n_begin_suppress, const int* eos, int n_eos, int min_new_tokens, int select, int64_t* tokens_out,
+                          int tok_off, int* state, const void* emb, int64_t ld_emb, int H, void* x_out, const int* bias_ids, const int* bias_seq_off,
+                          const float* bias_seq_bias, int n_bias_seqs, const int* bias_group_id, const float* bias_group_l1, const int* bias_group_off,
+                          int n_bias_groups, const int* bad_ids, const int* bad_seq_off, const float* bad_seq_bias, int n_bad_seqs, const int* bad_group_id,
+                          const float* bad_group_l1, const int* bad_group_off, int n_bad_groups, int min_length, const int* forced_eos, int n_forced_eos,
+                          const float* decay, int n_decay, int decay_start, int max_new_tokens, void* stream);
 /* The stopping rule of the decode step on the device (csrc/decode_stop.hip; generate(eos_token_id=[...], stop_strings=...)): ONE launch per step, a single block
  * (waves stride over the B rows, the lanes of a wave over the eos ids and the (stop string, end-length) pairs; any B >= 1).  Enqueue-only, no allocation, capturable.
  * t = *step_base + step_off = the index of the token JUST SELECTED (step_base: device int32, null = 0; the convention of afk_decode_sample); a t outside
