@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib, ops
+from . import decode_lookup as _lookup
 from . import decode_process as _process
 from . import decode_stop as _stop
 from ._lib import AfkError
@@ -85,6 +86,7 @@ def _run_steps(step, max_new, use_graph, closed, after=None):
 
 class AfkGenerationMixin:
     beam_on_device = os.environ.get("AFK_BEAM_DEVICE", "1") == "1"   # beam search: the step's decisions and the cache move as launches of the decode step (csrc/decode_beam.hip)
+    lookup_on_device = os.environ.get("AFK_LOOKUP_DEVICE", "1") == "1"   # prompt-lookup decoding: the draft and accept rules as launches of the step (csrc/decode_lookup.hip); off: torch ops and host reads
 
     # ------------------------------------------------------------------ the pieces of a step
     @staticmethod
@@ -313,7 +315,7 @@ class AfkGenerationMixin:
                  use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, min_p=None, typical_p=1.0,
                  epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, sequence_bias=None, bad_words_ids=None, min_length=0,
-                 forced_eos_token_id=None, exponential_decay_length_penalty=None, **kwargs):
+                 forced_eos_token_id=None, exponential_decay_length_penalty=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, **kwargs):
         """Greedy decoding, sampling or beam search on a KV cache, with GenerationMixin.generate's arguments and results; docs/generate.md describes every
         route, what it launches and how it differs from the reference.
 
@@ -330,12 +332,15 @@ class AfkGenerationMixin:
         eos_token_id (int, list, tuple or tensor) / pad_token_id (default: the first eos id) / stop_strings= with tokenizer=.
         logits_processor= / stopping_criteria= / streamer=: the reference's per-step hooks; with one of them the steps run eagerly.
         return_dict_in_generate= with output_scores= / output_logits=: an AfkGenerateOutput (sequences, scores, logits, past_key_values) in place of the ids.
+        prompt_lookup_num_tokens (k) with max_matching_ngram_size (2): prompt-lookup decoding - a step drafts up to k tokens by n-gram lookup in the ids so far,
+        verifies them in one pass over the weights and emits the confirmed ones plus one; the ids are the plain greedy ids.  Greedy, one sequence, KV cache.
         generation_config (default: self.generation_config if there is one) supplies every argument left at its default.
 
         Returns the ids [B * num_return_sequences, S0 + n]: the prompt, then the new tokens, pad_token_id behind a row's end.
 
         Raises ValueError where the reference's validation does (max_new_tokens <= 0, num_return_sequences, min_p / typical_p, eos / pad / stop_strings
-        forms, stop strings without a tokenizer) and AfkError for what is not built: unknown keywords, synced_gpus / use_model_defaults / assistant_model;
+        forms, stop strings without a tokenizer, prompt-lookup values <= 0 or a batch) and AfkError for what is not built: prompt-lookup decoding with anything
+        but plain greedy decoding of one sequence (decode_lookup.resolve); unknown keywords, synced_gpus / use_model_defaults / assistant_model;
         attention masks that are not left padding; beams with do_sample or use_cache=False; the logits processors, hooks, stop strings or the output
         object with beams or with use_cache=False; stop strings or the output object with AFK_EXACT_FP32=1; tokenizer= without a stop string;
         output_attentions / output_hidden_states."""
@@ -373,6 +378,10 @@ class AfkGenerationMixin:
         flags = _gout.resolve_output_flags(**out_kw, generation_config=gc, num_beams=int(num_beams), use_cache=bool(use_cache), exact_fp32=_exact.ENABLED)
         if int(max_new_tokens) <= 0:   # GenerationMixin refuses it as well (generation/configuration_utils.py validate())
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
+        # prompt-lookup decoding: keyword, else generation config; None: off, and nothing below changes
+        lookup = _lookup.resolve(prompt_lookup_num_tokens, max_matching_ngram_size, gc, batch_size=input_ids.shape[0], do_sample=bool(do_sample), num_beams=int(num_beams),
+                                 use_cache=bool(use_cache), exact_fp32=_exact.ENABLED, processors=spec.active or bool(procs), hooks=bool(criteria) or streamer is not None,
+                                 stop_strings=bool(stop_spec.stop_strings), output_object=flags.return_dict)
         if spec.active and (num_beams > 1 or not use_cache):
             raise AfkError("generate(repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens / sequence_bias / "
                            "bad_words_ids / min_length / forced_eos_token_id / exponential_decay_length_penalty): greedy or sampled decoding on the KV cache "
@@ -400,7 +409,8 @@ class AfkGenerationMixin:
         B, S0 = ids.shape
         dev = self.device_
         max_new = int(max_new_tokens)
-        lo, padded, Kc, Vt, pos_rows, krange, fast = self._prefill_setup(attention_mask, B, S0, max_new_tokens, "generate()")
+        # a lookup step writes the cache slots of all its k + 1 rows; only the accepted ones ever become visible, so the cache needs k more positions
+        lo, padded, Kc, Vt, pos_rows, krange, fast = self._prefill_setup(attention_mask, B, S0, max_new_tokens + (lookup.k if lookup else 0), "generate()")
         x = self._merged_embeddings(ids, input_features, input_features_mask)
         y = self._decode_layers(x, B, S0, 0, (Kc, Vt), pos_rows, krange, fast, kv_lo=lo if padded else None)
         last = y.reshape(B, S0, -1)[:, -1, :].contiguous()
@@ -408,6 +418,8 @@ class AfkGenerationMixin:
             return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), max_new, eos, pad, float(length_penalty), early_stopping, num_return=n_ret, use_graph=use_graph)
         first_logits = ops.gemm_nt(last, self.arena["lm_head.weight"].data).float()
         V = first_logits.shape[1]
+        if lookup is not None:
+            return self._generate_lookup(ids, first_logits, (Kc, Vt), lo, lookup, max_new, eos, use_graph)
         rec = None
         if flags.collect:   # one [max_new_tokens, B, V] fp32 buffer per kind, allocated once: static memory the captured step writes a slot of
             new_buf = lambda: torch.empty((max_new, B, V), device=dev, dtype=torch.float32)
@@ -461,6 +473,43 @@ class AfkGenerationMixin:
                 after = (new == eos1).cumsum(1) - (new == eos1).long() > 0
                 new = torch.where(after, torch.full_like(new, pad), new)
         return self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st.cache, lo)
+
+    @torch.no_grad()
+    def _generate_lookup(self, ids, first_logits, cache, lo, lookup, max_new, eos, use_graph):
+        """greedy decoding of one sequence by prompt lookup (decode_lookup.py): token 0 is the argmax of the prefill's logits; from then on a step is
+        afk_lookup_draft (up to k candidates from the ids so far + the k + 1 input rows) -> _lookup_forward (one pass over the weights, the rows appended at the
+        cache slots cur .. cur + k) -> afk_lookup_accept (row argmaxes, the confirmed prefix + one token, ids / tokens / status / [end, cur, position] advanced by
+        the number emitted).  Nothing in it depends on the host, so _run_steps captures and replays it; the host polls the status words every 8th step (steps
+        behind `done` change nothing) and reads the emitted tokens back once.  lookup_on_device = False: the two rules in torch ops with host reads around the
+        same forward, eagerly - the same ids and counters.  self.last_lookup_stats: {emitted, steps, accepted, rejecting} of the call and `launched`, the steps
+        enqueued (the device route learns of the end at its next poll: up to seven more than `steps`)."""
+        dev, S0, M = self.device_, ids.shape[1], lookup.k + 1
+        if S0 + max_new + lookup.k > int(self.config.text_config.max_position_embeddings):
+            raise AfkError(f"generate(prompt_lookup_num_tokens={lookup.k}): prompt {S0} + max_new_tokens {max_new} + {lookup.k} drafted positions exceed "
+                           f"max_position_embeddings {int(self.config.text_config.max_position_embeddings)}")
+        head, emb = self.arena["lm_head.weight"].data, self.arena[self._lm + "embed_tokens.weight"].data
+        state = torch.cat([lo, torch.tensor([S0 + 1, S0], device=dev, dtype=torch.int32), S0 - lo]).contiguous()   # [lo, key-range end, cache slot, position]
+        ls = _lookup.build_state(lookup, ids, self._select_token(first_logits), max_new, eos, state, emb.shape[1])
+        aws = self._decode_attn_workspace(dev, cache[1].shape[4], M) if self._lookup_chain_ok(M, head) else None
+        on_device = self.lookup_on_device
+        draft, accept = (_lookup.draft, _lookup.accept) if on_device else (_lookup.draft_host, _lookup.accept_host)
+
+        def step():
+            draft(ls, emb)
+            accept(ls, self._lookup_forward(ls["x"], cache, ls["pos"], ls["krange"], state[2:3], aws, head))
+
+        done = lambda t=0: ls["status"].tolist()[_lookup.DONE] != 0   # one small copy
+        launched = 0
+        if on_device:
+            launched = _run_steps(step, max_new, use_graph, done)
+        else:
+            while not done():
+                step()
+                launched += 1
+        st = ls["status"].tolist()
+        self.last_lookup_stats = dict(emitted=st[_lookup.EMITTED], steps=st[_lookup.STEPS], accepted=st[_lookup.ACCEPTED], rejecting=st[_lookup.REJECTING],
+                                      launched=launched)
+        return torch.cat([ids, ls["tokens"][None, :st[_lookup.EMITTED]]], dim=1)
 
     @staticmethod
     def _generate_output(flags, sequences, S0, rec, cache, lo):

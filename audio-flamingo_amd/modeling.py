@@ -1058,11 +1058,13 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, nn.Module):
     decode_norm_mode = os.environ.get("AFK_DECODE_NORM", "prologue")   # batched decode, four sequences and more: "prologue" | "producer" | "launch" (_decode_layers_chain_batched)
     decode_chain_batch = int(os.environ.get("AFK_DECODE_CHAIN_BATCH", "8"))   # largest batch the one-launch-per-Linear kernels take (0: single sequence only)
 
-    def _decode_layers_chain_batched(self, x, B, cache, pos_rows, krange, start_dev, aws, head):
+    def _decode_layers_chain_batched(self, x, B, cache, pos_rows, krange, start_dev, aws, head, one_sequence=False):
         """one new position of 2 .. 32 sequences: the single-sequence chain with M input rows per launch (`afk_decode_chain_*_batched`: the weights are still
         read once per step).  Round 6: 2 .. 8 sequences take the RMSNorm in the prologue of the Linear that consumes it (5 launches per layer), 9 .. 32 run as
         groups of eight behind one norm launch per norm (7 per layer); geometries the matrix-pipe launches do not take keep rounds 4-5's form (7 launches per
-        layer against ~12 on the split-K + glue path).  -> fp32 logits [B, V]"""
+        layer against ~12 on the split-K + glue path).  one_sequence: the B rows are CONSECUTIVE positions of the one sequence in the cache (the verify forward of
+        prompt-lookup decoding) - the qkv epilogue's batch strides become one cache slot (row m lands in slot *start_dev + m), the attention's become 0 (every row
+        reads the same cache, up to its own key-range end).  -> fp32 logits [B, V]"""
         a, lm, Hq, Hkv, D = self.arena, self._lm, self.Hq, self.Hkv, self.D
         Kc, Vt = cache
         Smax, Spad = Kc.shape[2], Vt.shape[4]
@@ -1073,6 +1075,7 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, nn.Module):
         st = ops._stream()
         ns = self._decode_attn_ws_check(aws, B, Spad)
         eps = float(self.rms_eps)
+        k_bs, vt_bs, ak_bs, avt_bs = (nk, 1, 0, 0) if one_sequence else (Smax * nk, Hkv * D * Spad, Smax * nk, Hkv * D * Spad)   # written per row / read per row
         q = torch.empty((B, nq), device=dev, dtype=torch.bfloat16)
         o = torch.empty((B, nq), device=dev, dtype=torch.bfloat16)
         # round 6: from two sequences on (the matrix-pipe regime of the batched launches) up to eight, no RMSNorm is a launch of its own.  "prologue" (default): the norm in
@@ -1096,15 +1099,15 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, nn.Module):
             wqkv = A("self_attn.qkv.weight").data
             if mode == "prologue":   # ssx: the partial sums of squares the previous layer's down launch left for these rows (None: the first layer takes the statistic itself)
                 _lib.call("afk_decode_chain_qkv_norm_batched", x.data_ptr(), x.stride(0), B, A("input_layernorm.weight").data.data_ptr(), eps, wqkv.data_ptr(), wqkv.stride(0), H,
-                          A("self_attn.qkv.bias").data.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos_rows.data_ptr(), q.data_ptr(), nq, Kc[i].data_ptr(), Smax * nk,
-                          Vt[i].data_ptr(), Hkv * D * Spad, Spad, start_dev.data_ptr(), Hq, Hkv, D, _p(ssx), H // 16, st)
+                          A("self_attn.qkv.bias").data.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos_rows.data_ptr(), q.data_ptr(), nq, Kc[i].data_ptr(), k_bs,
+                          Vt[i].data_ptr(), vt_bs, Spad, start_dev.data_ptr(), Hq, Hkv, D, _p(ssx), H // 16, st)
             else:
                 if h is None:
                     h, _ = ops.rmsnorm_fwd(x, A("input_layernorm.weight").data, eps)
                 _lib.call("afk_decode_chain_qkv_batched", h.data_ptr(), h.stride(0), B, wqkv.data_ptr(), wqkv.stride(0), H, A("self_attn.qkv.bias").data.data_ptr(),
-                          cos.data_ptr(), sin.data_ptr(), pos_rows.data_ptr(), q.data_ptr(), nq, Kc[i].data_ptr(), Smax * nk, Vt[i].data_ptr(), Hkv * D * Spad, Spad,
+                          cos.data_ptr(), sin.data_ptr(), pos_rows.data_ptr(), q.data_ptr(), nq, Kc[i].data_ptr(), k_bs, Vt[i].data_ptr(), vt_bs, Spad,
                           start_dev.data_ptr(), Hq, Hkv, D, st)
-            _lib.call("afk_attn_decode_fused", q.data_ptr(), nq, D, Kc[i].data_ptr(), Smax * nk, nk, D, Vt[i].data_ptr(), Hkv * D * Spad, Spad,
+            _lib.call("afk_attn_decode_fused", q.data_ptr(), nq, D, Kc[i].data_ptr(), ak_bs, nk, D, Vt[i].data_ptr(), avt_bs, Spad,
                       o.data_ptr(), nq, D, krange.data_ptr(), B, Hq, Hkv, D, float(D ** -0.5), ns, aws.data_ptr(), st)
             wo = A("self_attn.o_proj.weight").data
             x2 = torch.empty_like(x)
@@ -1217,6 +1220,21 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, nn.Module):
         else:
             y = self._decode_layers(x, B, 1, None, st.cache, pos1, kr1, False, start_dev=st.cur)
         return ops.gemm_nt(y, st.head).float()
+
+    def _lookup_chain_ok(self, M, head):
+        """the verify forward of M rows takes the one-launch-per-Linear batched chain (the conditions of _decode_logits' batched branch)"""
+        return self._chain_ok(1) and 2 <= M <= self._chain_batch_cap(head) and head.shape[0] % 8 == 0 and self.I % 4 == 0
+
+    def _lookup_forward(self, x, cache, pos_rows, krange, start_dev, aws, head):
+        """the verify forward of prompt-lookup decoding: M = x.shape[0] consecutive new positions of ONE sequence (embedding rows x [M, H], rotary positions
+        pos_rows [M], key ranges krange [M, 2] = [lo, end + j), cache slots *start_dev + j) in one pass over the decoder weights -> fp32 logits [M, V].  Up to
+        _chain_batch_cap rows: the batched decode chain with its cache strides aliased onto the one sequence; above (or where the chain does not apply):
+        _decode_layers on the interval kernel, then the lm_head GEMM."""
+        M = x.shape[0]
+        if self._lookup_chain_ok(M, head):
+            return self._decode_layers_chain_batched(x, M, cache, pos_rows, krange, start_dev, aws, head, one_sequence=True)
+        y = self._decode_layers(x, 1, M, None, cache, pos_rows, krange.view(1, M, 2), False, start_dev=start_dev)
+        return ops.gemm_nt(y, head).float()
 
     # gradient bookkeeping -------------------------------------------------------------------------
     def zero_grad(self, set_to_none: bool = False):

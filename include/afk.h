@@ -512,6 +512,42 @@ int afk_decode_process_ex(float* logits, int64_t ld_logits, int B, int V, int* h
 int afk_decode_stop(int64_t* next_token, int B, int* ids, int64_t ld_ids, int S0, int max_new, int* stop_at, int* status, const int* step_base, int step_off,
                     const int* eos, int n_eos, int pad, int feed_pad, const int* table, int rows, int vec, int P, int E, int S, const int* target_lens, int W,
                     void* stream);
+/* Prompt-lookup decoding on the device (csrc/decode_lookup.hip; generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=n), greedy, one sequence): the two
+ * host decisions of GenerationMixin._assisted_decoding around its verify forward, as launches.  Enqueue-only, no allocation, capturable; every position-dependent
+ * value is in device memory.  State of a call: ids [ids_cap] int32 = the prompt ids as passed to generate, then the emitted tokens; status
+ * [AFK_LOOKUP_STATUS_WORDS] int32 = {len (ids held), emitted, done, n_cand, steps, accepted, rejecting (steps that refused a candidate), n_match of the last step};
+ * state [4] int32 = {lo, key-range end, cache slot, position}, the step state of afk_decode_select_greedy.
+ *
+ * afk_lookup_draft = PromptLookupCandidateGenerator.get_candidates (transformers/generation/candidate_generator.py:1057-1150) on ids[0:len]:
+ *   1. for g = min(ngram, len - 1) down to 1 (:1076): the LEFTMOST window i with ids[i:i+g] == ids[len-g:len] (:1078-1092) whose continuation
+ *      ids[i+g : min(i+g+k, len)] is not empty (:1093-1097; the trailing window matches itself with an empty continuation and never wins).  The first g with such a
+ *      window decides.
+ *   2. the continuation is cropped in front of its first id in eos[n_eos] (:1132-1137) and to max_new - emitted - 1 ids, so that the accepted candidates and the
+ *      one token behind them never pass max_new (emitted == max_new - 1: no candidates, the reference's max_length == input_length + 1 return, :1071-1072).
+ *      If nothing is left there are NO candidates: no other window and no shorter g is tried (:1138-1144).  done != 0: no candidates.
+ *   3. out: status[3] = n_cand; cand [k] int32 (entries behind n_cand repeat ids[len-1]); the M = k + 1 input rows of the verify forward: rows [M] int64 =
+ *      {ids[len-1], cand[0 .. k)}, pos [M] = state[3] + j, krange [M][2] = {state[0], state[1] + j} (row j sees the cache up to its own slot); x_out (may be null:
+ *      no gather) [M][ldx] bf16 = emb[rows[j]][:H] (ids clamped to [0, vocab)).
+ *   One block; a history of any length up to ids_cap.  1 <= k <= AFK_LOOKUP_MAX_K, 1 <= ngram <= AFK_LOOKUP_MAX_NGRAM; with x_out: H % 8 == 0, 16-byte rows.
+ *
+ * afk_lookup_accept = the greedy branch of _assisted_decoding (transformers/generation/utils.py:3771-3786) on the fp32 logits [M][ld_logits] of that forward:
+ *   1. sel[j] = argmax of row j with the conventions of afk_decode_select_greedy: ties go to the lowest id, a NaN is never picked, a row with nothing finite
+ *      answers 0 (selected_tokens, :3771).  sel [M] int32 is written for every row.
+ *   2. n_match = the number of leading candidates j < n_cand (status[3]) with cand[j] == sel[j] (:3774).  The step emits sel[0 .. n_match], cut behind the first id
+ *      in eos[n_eos] among them and never past max_new (:3783-3786): e tokens.
+ *   3. ids[len + i] = tokens_out[emitted + i] = sel[i] for i < e (tokens_out [max_new] int64, may be null); len += e, emitted += e, state[1 .. 3] += e,
+ *      steps += 1, accepted += min(n_match, e), rejecting += (n_match < n_cand), status[7] = n_match; done = 1 on an eos id or at emitted == max_new.
+ *   With done != 0 on entry nothing is written at all, so replays behind the end are harmless.  Two kernels: AFK_LOOKUP_PARTS blocks per row take the argmax in
+ *   slices, one block folds them and does the bookkeeping.  ws: AFK_LOOKUP_WS_WORDS 4-byte words of scratch.  2 <= M <= AFK_LOOKUP_MAX_K + 1, V <= AFK_SAMPLE_MAX_V. */
+#define AFK_LOOKUP_MAX_K 31
+#define AFK_LOOKUP_MAX_NGRAM 16
+#define AFK_LOOKUP_STATUS_WORDS 8
+#define AFK_LOOKUP_PARTS 16
+#define AFK_LOOKUP_WS_WORDS 1024
+int afk_lookup_draft(const int* ids, int ids_cap, int* status, const int* state, int k, int ngram, int max_new, const int* eos, int n_eos, int* cand,
+                     int64_t* rows, int* pos, int* krange, const void* emb, int64_t ld_emb, int vocab, int H, void* x_out, int64_t ldx, void* stream);
+int afk_lookup_accept(const float* logits, int64_t ld_logits, int V, int M, const int* cand, int* ids, int ids_cap, int64_t* tokens_out, int max_new,
+                      int* status, int* state, const int* eos, int n_eos, int* sel, float* ws, void* stream);
 /* One step of beam search on the device (csrc/decode_beam.hip; generate(num_beams > 1)): what GenerationMixin._beam_search does between two forward passes
  * (transformers/generation/utils.py: _get_top_k_continuations, _update_finished_beams, _get_running_beams_for_next_iteration, _check_early_stop_heuristic,
  * _beam_search_has_unfinished_sequences), ONE call per generated token - two launches, a block per (row, beam) and a block per row - with no host state.
