@@ -84,6 +84,30 @@ def _run_steps(step, max_new, use_graph, closed, after=None):
     return n
 
 
+def continuation_lengths(P, S_total, who="generate(past_key_values=...)"):
+    """generate() on a passed cache: input_ids is the WHOLE conversation and the cache covers its first P positions (GenerationMixin._prefill,
+    transformers/generation/utils.py:3918-3938: "the `input_ids` are ... the FULL sequence, including previous inputs"; it slices
+    input_ids[:, -(S_total - P):] and has no check of its own for P >= S_total).  -> P; ValueError naming both numbers when nothing is left to run"""
+    P, S_total = int(P), int(S_total)
+    if P >= S_total:
+        raise ValueError(f"{who}: the cache already holds {P} positions and input_ids has {S_total}; input_ids must be the whole conversation, at least "
+                         f"one token longer than the cache")
+    return P
+
+
+def continuation_mask_check(attention_mask, lo, P, S_total, who="generate(past_key_values=...)"):
+    """the attention_mask of a continuation covers all S_total positions: its first P columns must be the left padding the cache records (zeros in front
+    of lo[b], ones from there) and the suffix all ones.  Anything else would be a hole in the keys a row sees, which the key-interval kernels cannot
+    express.  Pure: CPU or device tensors."""
+    if attention_mask.dim() != 2 or attention_mask.shape[0] != lo.shape[0] or attention_mask.shape[1] != int(S_total):
+        raise AfkError(f"{who}: attention_mask {tuple(attention_mask.shape)} must cover the whole conversation [{lo.shape[0]}, {int(S_total)}] (cache of "
+                       f"{int(P)} positions + the new ones)")
+    want = torch.arange(int(S_total), device=attention_mask.device)[None, :] >= lo.to(attention_mask.device)[:, None].long()
+    if not bool((attention_mask.bool() == want).all()):
+        raise AfkError(f"{who}: attention masks with holes are not supported - the first {int(P)} columns must repeat the left padding of the cache "
+                       f"(first real positions {lo.tolist()}) and the new positions must all be real")
+
+
 class AfkGenerationMixin:
     beam_on_device = os.environ.get("AFK_BEAM_DEVICE", "1") == "1"   # beam search: the step's decisions and the cache move as launches of the decode step (csrc/decode_beam.hip)
     lookup_on_device = os.environ.get("AFK_LOOKUP_DEVICE", "1") == "1"   # prompt-lookup decoding: the draft and accept rules as launches of the step (csrc/decode_lookup.hip); off: torch ops and host reads
@@ -334,6 +358,14 @@ class AfkGenerationMixin:
         return_dict_in_generate= with output_scores= / output_logits=: an AfkGenerateOutput (sequences, scores, logits, past_key_values) in place of the ids.
         prompt_lookup_num_tokens (k) with max_matching_ngram_size (2): prompt-lookup decoding - a step drafts up to k tokens by n-gram lookup in the ids so far,
         verifies them in one pass over the weights and emits the confirmed ones plus one; the ids are the plain greedy ids.  Greedy, one sequence, KV cache.
+        past_key_values (None): continue on a cache - the AfkKVCache a previous generate(return_dict_in_generate=True) or forward(use_cache=True) returned, or the
+        reference's DynamicCache.  The reference's semantics (GenerationMixin._prefill, transformers/generation/utils.py:3918-3938: input_ids is the FULL
+        sequence and is sliced to the positions the cache does not hold; _prepare_cache_for_generation :1946-1958 takes a user cache as it is;
+        prepare_inputs_for_generation :552 slices, :616 forwards the multimodal inputs on the first forward of a continuation; AF3 overrides none of them):
+        input_ids [B, S_total] is the whole conversation, the cache covers its first P positions, the model runs on ids[:, P:] (n rows behind a long past: the
+        split-KV append attention, afk_attn_append), input_features are the audio of the <sound> ids inside that suffix only, attention_mask covers S_total
+        (the cache's left padding, then ones).  The cache is updated in place - it holds every token but the last - and is the output object's
+        past_key_values.  Greedy or sampled decoding with everything below; docs/generate.md, "Continuing from a cache".
         generation_config (default: self.generation_config if there is one) supplies every argument left at its default.
 
         Returns the ids [B * num_return_sequences, S0 + n]: the prompt, then the new tokens, pad_token_id behind a row's end.
@@ -343,11 +375,13 @@ class AfkGenerationMixin:
         but plain greedy decoding of one sequence (decode_lookup.resolve); unknown keywords, synced_gpus / use_model_defaults / assistant_model;
         attention masks that are not left padding; beams with do_sample or use_cache=False; the logits processors, hooks, stop strings or the output
         object with beams or with use_cache=False; stop strings or the output object with AFK_EXACT_FP32=1; tokenizer= without a stop string;
-        output_attentions / output_hidden_states."""
+        output_attentions / output_hidden_states; past_key_values with num_beams > 1, use_cache=False, AFK_EXACT_FP32=1 or num_return_sequences > 1, with an
+        attention mask that has holes (AfkError), or with a cache that is not shorter than input_ids (ValueError naming both lengths)."""
         self._require_hip()
         procs, criteria, streamer = kwargs.pop("logits_processor", None), kwargs.pop("stopping_criteria", None), kwargs.pop("streamer", None)
         out_kw = {k: kwargs.pop(k, None) for k in ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")}
         stop_strings, tokenizer = kwargs.pop("stop_strings", None), kwargs.pop("tokenizer", None) or None
+        past = kwargs.pop("past_key_values", None)   # None: a fresh prefill, and not one launch or allocation differs
         for k in ("synced_gpus", "use_model_defaults", "assistant_model"):
             if kwargs.get(k):
                 raise AfkError(f"generate({k}=...) is not supported by this implementation")
@@ -376,6 +410,12 @@ class AfkGenerationMixin:
         eos, pad = stop_spec.eos, stop_spec.pad
         n_ret = _gout.resolve_num_return_sequences(num_return_sequences, generation_config=gc, num_beams=int(num_beams), do_sample=bool(do_sample))
         flags = _gout.resolve_output_flags(**out_kw, generation_config=gc, num_beams=int(num_beams), use_cache=bool(use_cache), exact_fp32=_exact.ENABLED)
+        if past is not None:
+            bad = [what for what, on in (("num_beams > 1", int(num_beams) > 1), ("use_cache=False", not use_cache), ("AFK_EXACT_FP32=1", _exact.ENABLED),
+                                         ("num_return_sequences > 1", n_ret > 1)) if on]
+            if bad:
+                raise AfkError(f"generate(past_key_values=...) with {' / '.join(bad)}: a passed cache continues greedy or sampled decoding of its own rows on "
+                               f"the KV cache only")
         if int(max_new_tokens) <= 0:   # GenerationMixin refuses it as well (generation/configuration_utils.py validate())
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         # prompt-lookup decoding: keyword, else generation config; None: off, and nothing below changes
@@ -410,16 +450,31 @@ class AfkGenerationMixin:
         dev = self.device_
         max_new = int(max_new_tokens)
         # a lookup step writes the cache slots of all its k + 1 rows; only the accepted ones ever become visible, so the cache needs k more positions
-        lo, padded, Kc, Vt, pos_rows, krange, fast = self._prefill_setup(attention_mask, B, S0, max_new_tokens + (lookup.k if lookup else 0), "generate()")
-        x = self._merged_embeddings(ids, input_features, input_features_mask)
-        y = self._decode_layers(x, B, S0, 0, (Kc, Vt), pos_rows, krange, fast, kv_lo=lo if padded else None)
-        last = y.reshape(B, S0, -1)[:, -1, :].contiguous()
+        headroom = max_new_tokens + (lookup.k if lookup else 0)
+        cont = self._continue_from(past, attention_mask, B, S0, headroom) if past is not None else None   # (the caller's object, its AfkKVCache form, P)
+        if cont is not None and cont[1] is not None:
+            # a passed cache: only the suffix ids[:, P:] runs - its <sound> rows take the audio of THIS call - as n new rows behind P cached positions, on the
+            # split-KV append attention; from `last` on the call is the one below, with S0 the whole conversation
+            kv, P = cont[1], cont[2]
+            lo, Kc, Vt, pos_rows, krange = self._continue_setup(kv, attention_mask, B, S0, headroom, "generate(past_key_values=...)")
+            x = self._merged_embeddings(ids[:, P:].contiguous(), input_features, input_features_mask)
+            y = self._decode_layers(x, B, S0 - P, P, (Kc, Vt), pos_rows, krange, False, append=True)
+            last = y.reshape(B, S0 - P, -1)[:, -1, :].contiguous()
+        else:
+            lo, padded, Kc, Vt, pos_rows, krange, fast = self._prefill_setup(attention_mask, B, S0, headroom, "generate()")
+            x = self._merged_embeddings(ids, input_features, input_features_mask)
+            y = self._decode_layers(x, B, S0, 0, (Kc, Vt), pos_rows, krange, fast, kv_lo=lo if padded else None)
+            last = y.reshape(B, S0, -1)[:, -1, :].contiguous()
+            if cont is not None:   # an EMPTY reference cache: the fresh prefill above (the LDS causal kernels, left padding included), written back at the end
+                from .modeling import AfkKVCache
+
+                cont = (cont[0], AfkKVCache(Kc, Vt, lo, 0), 0)
         if num_beams > 1:
             return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), max_new, eos, pad, float(length_penalty), early_stopping, num_return=n_ret, use_graph=use_graph)
         first_logits = ops.gemm_nt(last, self.arena["lm_head.weight"].data).float()
         V = first_logits.shape[1]
         if lookup is not None:
-            return self._generate_lookup(ids, first_logits, (Kc, Vt), lo, lookup, max_new, eos, use_graph)
+            return self._continue_done(cont, self._generate_lookup(ids, first_logits, (Kc, Vt), lo, lookup, max_new, eos, use_graph))
         rec = None
         if flags.collect:   # one [max_new_tokens, B, V] fp32 buffer per kind, allocated once: static memory the captured step writes a slot of
             new_buf = lambda: torch.empty((max_new, B, V), device=dev, dtype=torch.float32)
@@ -455,7 +510,7 @@ class AfkGenerationMixin:
                     od.part_val, od.part_idx = torch.empty(V // 8, device=dev, dtype=torch.float32), torch.empty(V // 8, device=dev, dtype=torch.int32)
         if hooks:
             seq = self._generate_with_hooks(ids, st, first_logits, max_new, procs, criteria, streamer, eos, pad)
-            return self._generate_output(flags, seq, S0, rec, st.cache, lo)
+            return self._continue_done(cont, self._generate_output(flags, seq, S0, rec, st.cache, lo))
         od = st.on_device
         toks = [st.nxt.clone()]
         eos1 = eos[0] if eos else None   # the scalar route (one eos id, no stop string): token buffers compared on the host, no stop launch
@@ -472,7 +527,36 @@ class AfkGenerationMixin:
             if eos1 is not None:  # everything after a row's first EOS becomes padding (GenerationMixin semantics)
                 after = (new == eos1).cumsum(1) - (new == eos1).long() > 0
                 new = torch.where(after, torch.full_like(new, pad), new)
-        return self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st.cache, lo)
+        return self._continue_done(cont, self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st.cache, lo))
+
+    def _continue_from(self, past, attention_mask, B, S_total, headroom):
+        """generate(past_key_values=past) -> (the caller's object, the AfkKVCache the call works on, P).  An AfkKVCache is worked on directly; the reference's
+        DynamicCache is adopted into one (AfkKVCache.adopt, as forward(past_key_values=...) adopts it) and written back at the end; an EMPTY DynamicCache
+        gives (past, None, 0): generate() runs its ordinary fresh prefill and writes the whole cache back."""
+        from .modeling import AfkKVCache
+
+        if isinstance(past, AfkKVCache):
+            return past, past, continuation_lengths(past.length, S_total)
+        if not AfkKVCache.is_reference_cache(past):
+            raise AfkError("generate(past_key_values=...): pass the AfkKVCache a previous generate(return_dict_in_generate=True) or forward(use_cache=True) returned, "
+                           "or the reference's DynamicCache")
+        P = continuation_lengths(past.get_seq_length(), S_total) if int(past.get_seq_length()) else 0
+        kv = AfkKVCache.adopt(past, self.dec_layers, self.Hkv, self.D, S_total - P, headroom, self.device_, attention_mask)
+        return past, kv, P   # kv None: the cache is empty
+
+    def _continue_done(self, cont, result):
+        """the end of a call on a passed cache: the AfkKVCache holds every token but the last (its K / Vt were replaced by _continue_setup if it grew), a
+        reference cache receives the positions [P, that length), and the output object carries the caller's own object"""
+        if cont is None:
+            return result
+        past, kv, P = cont
+        seq = result if torch.is_tensor(result) else result.sequences
+        kv.length = int(seq.shape[1]) - 1
+        if past is not kv:
+            kv.write_back(past, P, kv.length - P, self.Hkv, self.D)
+        if not torch.is_tensor(result):
+            result.past_key_values = past
+        return result
 
     @torch.no_grad()
     def _generate_lookup(self, ids, first_logits, cache, lo, lookup, max_new, eos, use_graph):

@@ -839,6 +839,33 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, nn.Module):
         fast = self.D in (64, 128) and ops.ATTN_IMPL == "lds" and (self.left_pad_on_lds_kernels or not padded)
         return lo, padded, Kc, Vt, pos_rows, krange, fast
 
+    def _continue_setup(self, cache, attention_mask, B, S_total, headroom, who):
+        """what a prefill of the suffix [P, S_total) on an EXISTING cache needs (P = cache.length; `who` names the caller in the error): the cache grown by
+        reallocation when S_total + headroom positions do not fit (once per turn: torch copies, as _forward_cached grows it) - `cache` is updated in place,
+        K / Vt replaced - the attention_mask held against the left padding the cache records (generation.continuation_mask_check), the rotary positions and
+        the key ranges of the suffix rows.  -> (lo, Kc, Vt, pos_rows, krange)"""
+        from .generation import continuation_lengths, continuation_mask_check
+
+        dev = self.device_
+        P = continuation_lengths(cache.length, S_total, who)
+        if cache.K.shape[1] != B or cache.K.shape[0] != self.dec_layers or cache.K.shape[3] != self.Hkv * self.D:
+            raise AfkError(f"{who}: past_key_values holds {cache.K.shape[0]} layers of {cache.K.shape[1]} rows x {cache.K.shape[3]} key columns; this call needs "
+                           f"{self.dec_layers} layers of {B} rows x {self.Hkv * self.D}")
+        lo = cache.lo.to(dev, torch.int32)
+        if attention_mask is not None:
+            continuation_mask_check(attention_mask.to(dev), lo, P, S_total, who)
+        Kc, Vt = cache.K, cache.Vt
+        if S_total + headroom > Kc.shape[2] or ops.pad64(S_total + headroom) > Vt.shape[4]:
+            Smax = S_total + headroom
+            K2 = torch.zeros((self.dec_layers, B, Smax, self.Hkv * self.D), device=dev, dtype=torch.bfloat16)
+            V2 = torch.zeros((self.dec_layers, B, self.Hkv, self.D, ops.pad64(Smax)), device=dev, dtype=torch.bfloat16)
+            K2[:, :, :P].copy_(Kc[:, :, :P])
+            V2[..., :P].copy_(Vt[..., :P])
+            Kc, Vt = K2, V2
+        cache.K, cache.Vt, cache.lo = Kc, Vt, lo
+        pos_rows, krange = self._pos_and_key_range(lo, P, S_total - P)
+        return lo, Kc, Vt, pos_rows, krange
+
     cache_headroom = 256  # forward(use_cache=True): positions reserved beyond the prompt; the cache grows by doubling when they run out
 
     @torch.no_grad()
@@ -899,16 +926,22 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, nn.Module):
             return AF3Output(logits=logits, past_key_values=new_cache.write_back(ref_cache, start, n, self.Hkv, self.D))
         return AF3Output(logits=logits, past_key_values=new_cache)
 
-    def _decode_layers(self, x, B, n, start, cache, pos_rows, krange, fast_prefill, start_dev=None, kv_lo=None):
+    def _decode_layers(self, x, B, n, start, cache, pos_rows, krange, fast_prefill, start_dev=None, kv_lo=None, append=False):
         """all decoder layers on n new positions per sample (rows [B*n, H]) at cache offset `start` (or *start_dev: graph replay).
         cache = (K [L, B, Smax, Hkv*D] post-RoPE keys, Vt [L, B, Hkv, D, Smaxpad] values stored transposed: the layout the interval
         attention kernels read directly).  Attention: prefill on the LDS-staged causal kernel (left-padded prompts: kv_lo); everything else
         (decode steps, other head sizes) on the interval kernel: query row i of sample b sees keys [krange[b,i,0], krange[b,i,1]);
-        with start_dev the kernel is given the whole cache length and the interval alone bounds what is visible."""
+        with start_dev the kernel is given the whole cache length and the interval alone bounds what is visible.
+        append (generate(past_key_values=...): a turn's rows behind a long past): the last branch launches the split-KV append kernel (afk_attn_append)
+        in place of the interval kernel where _append_routed says it wins; off (the default), every launch is what it was."""
         a, lm, Hq, Hkv, D = self.arena, self._lm, self.Hq, self.Hkv, self.D
         Kc, Vt = cache
         Smax, Spad = Kc.shape[2], Vt.shape[4]
         nq, nk = Hq * D, Hkv * D
+        append_ns, append_ws = 0, None
+        if append and not fast_prefill and self._append_routed(B, n, start + n):
+            append_ns = ops.attn_append_nsplit(B, Hq, Hkv, n, start + n)
+            append_ws = torch.empty(int(_lib.load().afk_attn_append_workspace_floats(B, Hq, n, D, append_ns)), device=x.device, dtype=torch.float32)
         cos, sin = self._rope_tables(int(self.config.text_config.max_position_embeddings))
         Sk = Smax if start_dev is not None else start + n
         for i in range(self.dec_layers):
@@ -929,6 +962,8 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, nn.Module):
                 _lib.call("afk_attn_decode", qkv.data_ptr(), qkv.stride(0), D, Kc[i].data_ptr(), Smax * nk, nk, D, Vt[i].data_ptr(),
                           Hkv * D * Spad, Spad, o.data_ptr(), nq, D, krange.data_ptr(), B, Hq, Hkv, D, float(D ** -0.5), ns,
                           ws.data_ptr(), ops._stream())
+            elif append_ns:
+                o = ops.attn_append(qkv, Kc[i], Vt[i], krange, B, n, Hq, Hkv, D, D ** -0.5, nsplit=append_ns, ws=append_ws)
             else:
                 o = torch.empty((B * n, nq), device=x.device, dtype=torch.bfloat16)
                 lse = torch.empty((B, Hq, n), device=x.device, dtype=torch.float32)
@@ -941,6 +976,22 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, nn.Module):
             x = ops.gemm_nt(ops.silu_mul_fwd(gu), A("mlp.down_proj.weight").data, residual=x2)
         y, _ = ops.rmsnorm_fwd(x, a[lm + "norm.weight"].data, self.rms_eps)
         return y
+
+    # _decode_layers(append=True) launches the append kernel only inside the envelope profiles/attn_append.md measured it to win in (by more than the spread):
+    # (Hq / Hkv, head_dim) -> (fewest visible keys, most samples).  Below 264 keys the interval kernel wins at every geometry (32 .. 136 keys: 7 - 12 us against 15)
+    append_envelope = {(7, 128): (264, 8), (1, 128): (264, 1), (2, 128): (264, 1), (4, 128): (264, 1), (8, 128): (264, 1), (2, 64): (321, 1)}
+    append_min_keys = 0     # a floor on top of the envelope (A/B: tools/bench_attn_append.py sets it above every length)
+
+    def _append_routed(self, B, n, keys):
+        """does a continuation of n rows per sample that sees up to `keys` keys go to afk_attn_append?  Only a geometry the kernel takes, a launch its
+        grid holds (ceil(n / rows per tile) * Hkv <= 65 535) and a shape inside the measured envelope; everything else stays on afk_xattn_fwd."""
+        if not ops.attn_append_supported(self.Hq, self.Hkv, self.D):
+            return False
+        G = self.Hq // self.Hkv
+        if -(-n // (32 // G)) * self.Hkv > 65535 or B > 65535:
+            return False
+        min_keys, max_batch = self.append_envelope.get((G, self.D), (1 << 62, 0))
+        return B <= max_batch and keys >= max(min_keys, self.append_min_keys)
 
     left_pad_on_lds_kernels = True  # left-padded batches on the LDS-staged causal kernels (kv_lo); False: interval kernels (A/B, tests)
     loss_on_valid_rows_only = True  # lm_head + CE (+ their backward GEMMs) on the rows with a label only (False: all B*S rows, as the reference)

@@ -699,6 +699,75 @@ def xattn_bwd(q, k, v, o, do, lse, krange, B, Sq, Sk, Hq, Hkv, D, scale, dq, dk,
               B, Hq, Hkv, Sq, Sk, sqp, skp, D, float(scale), _stream())
 
 
+ATTN_APPEND_MAX_SPLITS = 64      # afk_attn_append refuses more (csrc/attention_append.hip APPEND_MAX_SPLITS)
+ATTN_APPEND_GROUPS = (1, 2, 4, 7, 8)
+ATTN_APPEND_TARGET_BLOCKS = 256  # one block per CU: where the measured sweep turns (profiles/attn_append.md: 8 tiles x 32, 64 tiles x 4, 768 tiles x 1)
+ATTN_APPEND_MIN_CHUNK = 128      # keys: the shortest chunk that still paid for its block and its share of the merge (1 032 keys: 8 splits)
+ATTN_APPEND_RULE_SPLITS = 16     # most splits the rule asks for: no measured shape was faster by more than 3 % with more, and few-tile launches lost 60 % at 64
+
+
+def attn_append_supported(Hq, Hkv, D):
+    """the geometries afk_attn_append takes"""
+    return D in (64, 128) and Hkv > 0 and Hq % Hkv == 0 and Hq // Hkv in ATTN_APPEND_GROUPS
+
+
+def attn_append_nsplit(B, Hq, Hkv, n, keys):
+    """key splits of afk_attn_append from the shape alone (no device read): the launch has B * Hkv * ceil(n / rows per tile) query tiles; split until
+    ATTN_APPEND_TARGET_BLOCKS blocks exist, but never into chunks shorter than ATTN_APPEND_MIN_CHUNK of the `keys` a row can see at most, and never more
+    than ATTN_APPEND_RULE_SPLITS (the kernel itself takes up to ATTN_APPEND_MAX_SPLITS).  Always >= 1."""
+    tiles = max(1, B * Hkv * -(-max(int(n), 1) // (32 // max(Hq // Hkv, 1))))
+    ns = -(-ATTN_APPEND_TARGET_BLOCKS // tiles)
+    return max(1, min(ns, max(int(keys), 0) // ATTN_APPEND_MIN_CHUNK, ATTN_APPEND_RULE_SPLITS))
+
+
+def attn_append_chunks(lo, hi, ns):
+    """the key chunks afk_attn_append cuts the hull [lo, hi) of a query tile into: a0 = lo & ~31, chunk = round32(ceil((hi - a0) / ns)), split s = keys
+    [max(a0 + s * chunk, lo), min(a0 + (s + 1) * chunk, hi)) -> [(begin, end)], empty splits as (x, x)"""
+    if hi <= lo:
+        return [(lo, lo)] * ns
+    a0 = lo & ~31
+    chunk = ((-(-(hi - a0) // ns)) + 31) & ~31
+    out = []
+    for s in range(ns):
+        c0, c1 = a0 + s * chunk, min(a0 + (s + 1) * chunk, hi)
+        out.append((max(c0, lo), c1) if c1 > c0 else (hi, hi))
+    return out
+
+
+def attn_append(q, Kc, Vt, krange, B, n, Hq, Hkv, D, scale, nsplit=None, ws=None, out=None):
+    """append attention (afk_attn_append): n new query rows per sample against the KV cache, split-KV, two launches.  q [B*n, >= Hq*D] row-strided view
+    (post-RoPE), Kc [B, Smax, Hkv*D], Vt [B, Hkv, D, spad] (one layer of the cache), krange [B, n, 2] int32 on the device: row i of sample b sees keys
+    [krange[b,i,0], krange[b,i,1]).  nsplit None: attn_append_nsplit over the cache rows.  ws: a float32 workspace of at least
+    afk_attn_append_workspace_floats(B, Hq, n, D, nsplit) elements (None: allocated here).  -> o [B*n, Hq*D] bf16"""
+    _chk(q, BF16, "q"), _chk(Kc, BF16, "Kc"), _chk(Vt, BF16, "Vt")
+    if krange is not None:
+        _chk(krange, torch.int32, "krange")
+    if q.dim() != 2 or q.shape[0] != B * n or q.shape[1] < Hq * D or q.stride(1) != 1:
+        raise AfkError(f"attn_append: q {tuple(q.shape)} strides {q.stride()} is not [B*n = {B * n}, >= Hq*D = {Hq * D}] with unit column stride")
+    if tuple(Kc.shape) != (B, Kc.shape[1], Hkv * D) or Kc.stride(2) != 1:
+        raise AfkError(f"attn_append: Kc {tuple(Kc.shape)} strides {Kc.stride()} is not [B = {B}, Smax, Hkv*D = {Hkv * D}] with unit column stride")
+    Smax, spad = Kc.shape[1], Vt.shape[3]
+    if tuple(Vt.shape) != (B, Hkv, D, spad) or Vt.stride()[1:] != (D * spad, spad, 1):
+        raise AfkError(f"attn_append: Vt {tuple(Vt.shape)} strides {Vt.stride()} is not [B = {B}, Hkv = {Hkv}, D = {D}, spad] with its heads and features contiguous")
+    if krange is not None and (tuple(krange.shape) != (B, n, 2) or not krange.is_contiguous()):
+        raise AfkError(f"attn_append: krange {tuple(krange.shape)} is not a contiguous [B = {B}, n = {n}, 2]")
+    ns = attn_append_nsplit(B, Hq, Hkv, n, Smax) if nsplit is None else int(nsplit)
+    if ws is None:
+        ws = torch.empty(int(_lib.load().afk_attn_append_workspace_floats(B, Hq, n, D, max(min(ns, ATTN_APPEND_MAX_SPLITS), 1))), device=q.device, dtype=torch.float32)
+    else:
+        _chk(ws, torch.float32, "ws")
+    if out is None:
+        o = torch.empty((B * n, Hq * D), device=q.device, dtype=BF16)
+    else:
+        o = _chk(out, BF16, "out")
+        if tuple(o.shape) != (B * n, Hq * D) or o.stride(1) != 1:
+            raise AfkError(f"attn_append: out {tuple(o.shape)} strides {o.stride()} is not [B*n, Hq*D] with unit column stride")
+    # the strides are the tensors' own: a cache view with a longer row or sample pitch is read as it lies
+    _lib.call("afk_attn_append", q.data_ptr(), n * q.stride(0), D, q.stride(0), Kc.data_ptr(), Kc.stride(0), Kc.stride(1), D, Vt.data_ptr(), Vt.stride(0), spad,
+              o.data_ptr(), n * o.stride(0), D, o.stride(0), _p(krange), B, Hq, Hkv, n, D, float(scale), ns, ws.data_ptr(), ws.numel(), _stream())
+    return o
+
+
 def attn_interval_fwd(qkv, krange, B, S, Hq, Hkv, D, *, scale):
     """self-attention on a fused q|k|v projection with a per-query key interval (left / right / both-side padding, causal or not)"""
     _chk(qkv, BF16, "qkv")

@@ -341,6 +341,27 @@ int afk_attn_decode_fused(const void* Q, int64_t q_bs, int64_t q_hs, const void*
  * Env AFK_ATTN_DECODE_GROUP sets the initial mode. */
 int afk_attn_decode_set_group(int mode);
 
+/* Append attention (csrc/attention_append.hip): n NEW query rows per sample against the KV cache - a chat turn behind a long past (Qwen2Attention.forward with
+ * past_key_values and more than one new position, modeling_qwen2.py:195-234).  Forward only, split-KV, two plain launches (partials, then the merge in split
+ * order): no counters, no atomics, the result depends on the inputs and nsplit alone.  Operands are those afk_xattn_fwd is given by the decode path:
+ * Q rows inside the fused projection (post-RoPE; strides q_bs per sample, q_hs per head, q_rs per row), K cache [B][pos][Hkv][D] (k_bs, k_rs, k_hs), V^T cache
+ * [B][Hkv][D][spad] (vt_bs) as written by afk_kv_cache_append, O [B][n][Hq][D] by strides (o_bs, o_hs, o_rs); bf16 in and out, fp32 scores, softmax and
+ * accumulation, probabilities rounded to bf16 in front of P.V.  krange[B][n][2] (int32, DEVICE memory, read by the kernel: capturable): query row i of sample b
+ * sees keys [krange[b,i,0], krange[b,i,1]) - any intervals, not only the causal staircase [lo_b, start + i + 1); an empty interval gives a zero row (+0.0, the
+ * bits afk_xattn_fwd writes).  Interval ends must lie inside the cache rows (they are clamped to spad).  What may hold anything, NaN included: cache slots
+ * and V^T columns OUTSIDE THE HULL of a query tile's intervals (a tile = 32 / (Hq / Hkv) consecutive rows of a sample: from its smallest begin to its largest
+ * end) - so every slot behind the last interval end of a sample or in front of its first begin, and the pad columns of V^T.  A slot INSIDE a tile's hull that
+ * no row of the tile sees (a gap between two disjoint intervals) is still multiplied by a zero probability: it must hold finite values, as afk_xattn_fwd
+ * requires of every slot its tiles touch.
+ * head_dim 64 / 128; Hq / Hkv in {1, 2, 4, 7, 8}: the heads of a group share the 32 columns of one MFMA tile with 32 / (Hq / Hkv) query rows; any n >= 1 with
+ * ceil(n / rows per tile) * Hkv <= 65 535; any key count.  1 <= nsplit <= 64: each tile's own key hull is cut into nsplit chunks on 32-key boundaries.
+ * ws: ws_floats >= afk_attn_append_workspace_floats(B, Hq, n, D, nsplit) floats, 16-byte aligned, no initial contents required.  spad % 32 == 0, element strides
+ * of Q / K % 8 == 0.  Everything else is refused with AFK_ERR_ARG. */
+int64_t afk_attn_append_workspace_floats(int B, int Hq, int n, int D, int nsplit);
+int afk_attn_append(const void* Q, int64_t q_bs, int64_t q_hs, int64_t q_rs, const void* Kc, int64_t k_bs, int64_t k_rs, int64_t k_hs,
+                    const void* Vt, int64_t vt_bs, int spad, void* O, int64_t o_bs, int64_t o_hs, int64_t o_rs, const int* krange, int B,
+                    int Hq, int Hkv, int n, int D, float scale, int nsplit, float* ws, int64_t ws_floats, void* stream);
+
 /* Decode-step glue (csrc/decode_glue.hip): the weight-streaming first pass alone, and one kernel per Linear of a decoder layer that sums
  * its fp32 partials ws[splits][M][N] and applies everything up to the next Linear's input (one live row per call today: M <= AFK_GEMV_MAX_M; same arithmetic and bf16
  * rounding points as the stand-alone kernels; oracle lines: modeling_qwen2.py:46-48, 112-135, 213-214, 247-252, 284-297). */
