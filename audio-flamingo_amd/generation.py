@@ -1,5 +1,5 @@
 """generate() of the MI355X-native Audio Flamingo 3 model: greedy decoding, sampling and beam search on the KV cache, host code only (docs/generate.md
-tells the routes feature by feature; the forward pieces a step runs - _decode_logits, _decode_layers*, _chain_* - live in modeling.py).
+tells the routes feature by feature; the forward pieces a step runs - _decode_logits, _decode_layers*, _chain_* - live in decode_forward.py).
 
   DecodeState        the record a decode step works on: the cache, the static device tensors, what the step applies
   _run_steps         the loop every route drives its step with: eager, captured at the second step, replayed, polled every eighth

@@ -77,7 +77,7 @@ def _append(q, kc, vt, kr, B, n, Hq, Hkv, D, ns):
 
 
 def _xattn(q, kc, vt, kr, B, n, Hq, Hkv, D, Sk):
-    """the launch of modeling._decode_layers' last branch"""
+    """the launch of decode_forward._decode_layers' last branch"""
     ops, lib = _mods()
     nq, nk = Hq * D, Hkv * D
     Smax, spad = kc.shape[1], vt.shape[3]

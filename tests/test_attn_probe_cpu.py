@@ -76,7 +76,7 @@ def test_decode_chunk_edges_match_the_kernel_formula():
 
 
 def test_host_decode_split_choice():
-    """modeling._decode_nsplit: decode_splits while 4 096-key chunks cover the cache, ceil(spad / 4096) beyond, refused above the one-launch merge's limit;
+    """decode_forward._decode_nsplit: decode_splits while 4 096-key chunks cover the cache, ceil(spad / 4096) beyond, refused above the one-launch merge's limit;
     the workspace is sized for the same count"""
     from audio_flamingo_amd import _lib
     from audio_flamingo_amd.modeling import AudioFlamingo3ForConditionalGeneration as Mine

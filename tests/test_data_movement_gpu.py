@@ -1,6 +1,6 @@
 """The kernels of csrc/elementwise.hip that only move data, on an MI355X against tests/_frontend_ref.py, BIT for bit (int16 views: -0 and NaN payloads
 count): the conv stem's im2col / col2im / weight permutation / AvgPool, placeholder_scan, the embedding gather / scatter and its row gather / scatter
-form, transpose (with the persistent loop ops.THIN_BLOCKS switches on) and transpose_heads, afk_kv_cache_append as modeling.py calls it, cast_f32_bf16 -
+form, transpose (with the persistent loop ops.THIN_BLOCKS switches on) and transpose_heads, afk_kv_cache_append as decode_forward.py calls it, cast_f32_bf16 -
 and rotary_time, the one kernel here that does arithmetic, within its derived bound of the float64 formula.  Every output is NaN before the call;
 where the wrapper allocates it, the C entry point is called a second time on a view inside a larger NaN buffer whose guard must stay untouched.
 Each family is run at one vector, at its tile / wave / chunk seams and past ew_grid's 1,048,576-item cap (tests/test_frontend_ref_cpu.py asserts that
@@ -341,7 +341,7 @@ def test_rotary_time(dev, rows, E, Rr):
 @pytest.mark.parametrize("start", R.KV_STARTS)
 @pytest.mark.parametrize("B,n,Hkv,D", R.KV_CASES)
 def test_kv_cache_append(dev, B, n, Hkv, D, start, from_device):
-    """as modeling.py calls it: k_col0 = Hq D into a row wider than q | k | v, caches longer than start + n with Spad != Smax.  With start_dev given,
+    """as decode_forward.py calls it: k_col0 = Hq D into a row wider than q | k | v, caches longer than start + n with Spad != Smax.  With start_dev given,
     start_host holds another (in-bounds) value: the device value must win"""
     ops = _ops()
     Hq, nk = 2 * Hkv, Hkv * D

@@ -24,7 +24,7 @@ def _cfg():
 
 
 def test_decode_batch_routing_host_logic():
-    """which batches take the one-launch-per-Linear decode step (host logic of modeling._chain_batch_cap / _prologue_shapes_ok, round 6): the tiny test geometry
+    """which batches take the one-launch-per-Linear decode step (host logic of decode_forward._chain_batch_cap / _prologue_shapes_ok, round 6): the tiny test geometry
     (hidden 256, 4:2 x 64 heads) and the AF3-7B geometry take the norm-in-prologue launches up to 8 sequences and groups of eight up to 32; AFK_DECODE_CHAIN_BATCH_MAX
     caps it; a geometry the 64-element blocks do not divide, or another norm mode, stays at eight sequences on rounds 4-5's launches"""
     import types
