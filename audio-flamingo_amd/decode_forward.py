@@ -403,15 +403,18 @@ class AfkDecodeForwardMixin:
             return logits
         return ops.rmsnorm_fwd(x, self.arena[self._lm + "norm.weight"].data, self.rms_eps)[0]
 
-    def _decode_layers_chain_batched(self, x, B, cache, pos_rows, krange, start_dev, aws, head, one_sequence=False):
+    def _decode_layers_chain_batched(self, x, B, cache, pos_rows, krange, start_dev, aws, head, one_sequence=False, shared=None):
         """one new position of 2 .. 32 sequences: the single-sequence chain with M input rows per launch (`afk_decode_chain_*_batched`: the weights are still
         read once per step).  Round 6: 2 .. 8 sequences take the RMSNorm in the prologue of the Linear that consumes it (5 launches per layer), 9 .. 32 run as
         groups of eight behind one norm launch per norm (7 per layer); geometries the matrix-pipe launches do not take keep rounds 4-5's form (7 launches per
         layer against ~12 on the split-K + glue path).  one_sequence: the B rows are CONSECUTIVE positions of the one sequence in the cache (the verify forward of
-        prompt-lookup decoding): row m lands in slot *start_dev + m and every row reads the same cache (CacheGeometry's k_write .. vt_read).  -> fp32 logits [B, V]"""
+        prompt-lookup decoding): row m lands in slot *start_dev + m and every row reads the same cache (CacheGeometry's k_write .. vt_read).
+        shared (a decode_share.SharedPrompt): `cache` is the TAIL cache of the B = B0 * n continuations - the qkv launch appends to it as it is told to - and
+        the attention launch is afk_attn_decode_shared over the prompt cache (prompt keys shared.prange) and the tail (krange = [B, 2]: the tail keys);
+        aws is its workspace.  Nothing else in the loop differs.  -> fp32 logits [B, V]"""
         g, w = CacheGeometry.of(self, cache, one_sequence=one_sequence), self._w
         Hq, Hkv, D, H, nq, eps, st, dev = g.Hq, g.Hkv, g.D, g.H, g.nq, g.eps, g.stream, x.device
-        ns = self._decode_attn_ws_check(aws, B, g.Spad)
+        ns = self._decode_attn_ws_check(aws, B, g.Spad) if shared is None else shared.nsplit
         cos, sin, pos, start = g.cos.data_ptr(), g.sin.data_ptr(), pos_rows.data_ptr(), start_dev.data_ptr()
         q = torch.empty((B, nq), device=dev, dtype=torch.bfloat16)
         o = torch.empty((B, nq), device=dev, dtype=torch.bfloat16)
@@ -440,8 +443,15 @@ class AfkDecodeForwardMixin:
                     h, _ = ops.rmsnorm_fwd(x, w(i, "input_layernorm.weight"), eps)
                 _lib.call("afk_decode_chain_qkv_batched", h.data_ptr(), h.stride(0), B, wqkv.data_ptr(), wqkv.stride(0), H, bias,
                           cos, sin, pos, q.data_ptr(), nq, g.k(i), g.k_write, g.vt(i), g.vt_write, g.vt_row, start, Hq, Hkv, D, st)
-            _lib.call("afk_attn_decode_fused", q.data_ptr(), nq, D, g.k(i), g.k_read, g.k_row, D, g.vt(i), g.vt_read, g.vt_row,
-                      o.data_ptr(), nq, D, krange.data_ptr(), B, Hq, Hkv, D, float(D ** -0.5), ns, aws.data_ptr(), st)
+            if shared is None:
+                _lib.call("afk_attn_decode_fused", q.data_ptr(), nq, D, g.k(i), g.k_read, g.k_row, D, g.vt(i), g.vt_read, g.vt_row,
+                          o.data_ptr(), nq, D, krange.data_ptr(), B, Hq, Hkv, D, float(D ** -0.5), ns, aws.data_ptr(), st)
+            else:
+                # the caches and intervals were checked once (decode_share.build -> ops.attn_shared_check); the prompt cache is contiguous: its pitches are spelled here
+                Kp, Vtp = shared.cache
+                _lib.call("afk_attn_decode_shared", q.data_ptr(), nq, D, Kp[i].data_ptr(), shared.S0 * g.nk, g.nk, D, Vtp[i].data_ptr(), Hkv * D * Vtp.shape[4],
+                          Vtp.shape[4], shared.S0, g.k(i), g.k_sample, g.k_row, D, g.vt(i), g.vt_sample, g.vt_row, g.Smax, o.data_ptr(), nq, D,
+                          shared.prange.data_ptr(), krange.data_ptr(), B // shared.n, shared.n, Hq, Hkv, D, float(D ** -0.5), ns, aws.data_ptr(), aws.numel(), st)
             wo, norm2 = w(i, "self_attn.o_proj.weight"), w(i, "post_attention_layernorm.weight")
             x2, h2 = torch.empty_like(x), None
             if mode == "producer":
@@ -512,6 +522,12 @@ class AfkDecodeForwardMixin:
         """logits [B, V] (fp32) of the position after st.nxt (a generation.DecodeState): one pass over the decoder weights, cache append at st.cur (not advanced here)"""
         B = st.nxt.shape[0]
         x = st.emb.index_select(0, st.nxt)
+        if st.shared is not None:
+            # a shared prompt cache (decode_share.py): st.cache is the tail cache and st.cur its slot, from 0 - the new position is S0 - lo + cur, the visible
+            # tail keys are [0, cur + 1).  Only the batched chain has the route (generate() resolved that before the prefill)
+            sh = st.shared
+            sh.trange[:, 1:].copy_((st.cur + 1).expand(B, 1))
+            return self._decode_layers_chain_batched(x.contiguous(), B, st.cache, sh.pos0 + st.cur, sh.trange, st.cur, sh.ws, st.head, shared=sh)
         if st.single is not None:   # single sequence (generate()): views of the step-state tensor, advanced by ONE add per step
             pos1, kr1 = st.single.pos1, st.single.kr1
         else:

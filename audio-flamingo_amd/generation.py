@@ -15,6 +15,7 @@ import torch
 from . import _lib, ops
 from . import decode_lookup as _lookup
 from . import decode_process as _process
+from . import decode_share as _share
 from . import decode_stop as _stop
 from ._lib import AfkError
 
@@ -55,6 +56,7 @@ class DecodeState:
     tok_off: Optional[int] = None     # token number = *cur + tok_off
     single: Optional[SingleSequence] = None
     on_device: Optional[OnDevice] = None
+    shared: Optional[_share.SharedPrompt] = None   # the prompt cache of a call that shares it (decode_share.py): `cache` is then the TAIL cache, cur counts its slots from 0
 
 
 def _run_steps(step, max_new, use_graph, closed, after=None):
@@ -111,6 +113,8 @@ def continuation_mask_check(attention_mask, lo, P, S_total, who="generate(past_k
 class AfkGenerationMixin:
     beam_on_device = os.environ.get("AFK_BEAM_DEVICE", "1") == "1"   # beam search: the step's decisions and the cache move as launches of the decode step (csrc/decode_beam.hip)
     lookup_on_device = os.environ.get("AFK_LOOKUP_DEVICE", "1") == "1"   # prompt-lookup decoding: the draft and accept rules as launches of the step (csrc/decode_lookup.hip); off: torch ops and host reads
+    share_prompt_cache = os.environ.get("AFK_SHARE_PROMPT", "0") == "1"   # generate(share_prompt=None): sampled copies and device beams share the prompt's keys (decode_share.py, csrc/attention_shared.hip)
+    last_share_stats = None   # the last generate() call that shared a prompt cache: decode_share.stats; None after every other call
 
     # ------------------------------------------------------------------ the pieces of a step
     @staticmethod
@@ -226,7 +230,7 @@ class AfkGenerationMixin:
 
     # ------------------------------------------------------------------ beam search
     @torch.no_grad()
-    def _beam_search(self, ids, last_hidden, cache, lo, nb, max_new, eos, pad, length_penalty, early_stopping, *, num_return=1, use_graph=None):
+    def _beam_search(self, ids, last_hidden, cache, lo, nb, max_new, eos, pad, length_penalty, early_stopping, *, num_return=1, use_graph=None, share=None):
         """Beam search on the KV cache with GenerationMixin's scoring (transformers/generation/utils.py:3008-3400): every batch row keeps `nb`
         running beams ranked by accumulated log-probability; at each step the best (n_eos + 1) * nb continuations over all beams are drawn, the
         ones among the top nb that end (EOS, or the length limit) compete for the row's nb FINISHED slots with score = sum / generated_length ^
@@ -242,6 +246,9 @@ class AfkGenerationMixin:
         dev = self.device_
         B, S0 = ids.shape
         V = self.V
+        if share is not None:   # the prompt cache is the prefill's own (no headroom, no per-beam copy); the beams' generated positions live in a tail cache
+            shared, tail, lo_rep, rep = self._share_setup(share, cache, lo, S0, max_new)
+            return self._beam_search_device(ids, last_hidden, tail, lo_rep, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph, shared=shared)
         rep = torch.arange(B, device=dev).repeat_interleave(nb)   # one cache row per beam
         Kc, Vt = cache[0].index_select(1, rep).contiguous(), cache[1].index_select(1, rep).contiguous()
         lo = lo.index_select(0, rep).contiguous()
@@ -310,16 +317,20 @@ class AfkGenerationMixin:
         return torch.cat([ids.repeat_interleave(n, dim=0) if n > 1 else ids, best_seq[:, : int(best_len.max())]], dim=1)
 
     @torch.no_grad()
-    def _beam_search_device(self, ids, last_hidden, cache, lo, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph):
+    def _beam_search_device(self, ids, last_hidden, cache, lo, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph, shared=None):
         """_beam_search with every per-token decision on the device (cache, lo: one row per beam, rep: each one's prompt row).  A step is _decode_logits -> afk_beam_step (log-softmax, the row's top (n_eos + 1) * nb
         continuations, finished slots, running beams, the early-stop heuristic, {t, open} in a status word) -> afk_beam_reorder_cache (the slots written since
         the prompt move by parentage, in place: the beams of a row share their prompt keys bit for bit) -> cur += 1; nothing in it depends on the host, so it is
         captured and replayed (_run_steps).  Token 0 runs eagerly with the kernel of the captured steps.  The host polls the status word every 8th step (steps
-        behind the closing one write nothing) and reads the finished hypotheses back once."""
+        behind the closing one write nothing) and reads the finished hypotheses back once.
+        shared (generate(share_prompt=True)): `cache` is the tail cache and the prompt keys stay in the prefill's own cache, one row per prompt row - the
+        slots count from 0, so the reorder moves the slots 0 .. cur of the tail and no prompt key is ever copied."""
         B, S0 = ids.shape
         Kc, Vt = cache
         bs = ops.beam_state(B, nb, max_new, device=self.device_, eos=eos, length_penalty=length_penalty, early_stopping=early_stopping)
-        st = self._new_state(cache, lo, S0, bs["next_token"])
+        if shared is not None:
+            S0 = 0   # of the cache the step appends to
+        st = self._new_state(cache, lo, S0, bs["next_token"], shared=shared)
         ops.beam_step(ops.gemm_nt(last_hidden, st.head).float().index_select(0, rep).contiguous(), bs, step_off=0)
 
         def step():   # token t = cur + 1 - S0: the forward pass appends the keys of token t - 1 at slot cur, so the slots S0 .. cur move
@@ -339,7 +350,7 @@ class AfkGenerationMixin:
                  use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, min_p=None, typical_p=1.0,
                  epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, sequence_bias=None, bad_words_ids=None, min_length=0,
-                 forced_eos_token_id=None, exponential_decay_length_penalty=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, **kwargs):
+                 forced_eos_token_id=None, exponential_decay_length_penalty=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, share_prompt=None, **kwargs):
         """Greedy decoding, sampling or beam search on a KV cache, with GenerationMixin.generate's arguments and results; docs/generate.md describes every
         route, what it launches and how it differs from the reference.
 
@@ -366,6 +377,10 @@ class AfkGenerationMixin:
         split-KV append attention, afk_attn_append), input_features are the audio of the <sound> ids inside that suffix only, attention_mask covers S_total
         (the cache's left padding, then ones).  The cache is updated in place - it holds every token but the last - and is the output object's
         past_key_values.  Greedy or sampled decoding with everything below; docs/generate.md, "Continuing from a cache".
+        share_prompt (None: the class attribute share_prompt_cache, env AFK_SHARE_PROMPT, default off): the sampled copies (do_sample with
+        num_return_sequences = n) or the device beams of a row share ONE prefill and ONE copy of the prompt's keys; a step attends to the prompt cache and
+        a short tail cache of generated positions (afk_attn_decode_shared).  False, or nothing to share: not one launch or allocation differs.  The ids can
+        differ from the unshared call on near-ties (the prefill runs on other row counts); docs/generate.md, "Sharing the prompt".
         generation_config (default: self.generation_config if there is one) supplies every argument left at its default.
 
         Returns the ids [B * num_return_sequences, S0 + n]: the prompt, then the new tokens, pad_token_id behind a row's end.
@@ -376,8 +391,11 @@ class AfkGenerationMixin:
         attention masks that are not left padding; beams with do_sample or use_cache=False; the logits processors, hooks, stop strings or the output
         object with beams or with use_cache=False; stop strings or the output object with AFK_EXACT_FP32=1; tokenizer= without a stop string;
         output_attentions / output_hidden_states; past_key_values with num_beams > 1, use_cache=False, AFK_EXACT_FP32=1 or num_return_sequences > 1, with an
-        attention mask that has holes (AfkError), or with a cache that is not shorter than input_ids (ValueError naming both lengths)."""
+        attention mask that has holes (AfkError), or with a cache that is not shorter than input_ids (ValueError naming both lengths); share_prompt=True
+        with use_cache=False, AFK_EXACT_FP32=1, past_key_values, the per-step hooks, prompt-lookup decoding, the host beam loop or a geometry outside the
+        batched decode chain (decode_share.resolve)."""
         self._require_hip()
+        self.last_share_stats = None
         procs, criteria, streamer = kwargs.pop("logits_processor", None), kwargs.pop("stopping_criteria", None), kwargs.pop("streamer", None)
         out_kw = {k: kwargs.pop(k, None) for k in ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")}
         stop_strings, tokenizer = kwargs.pop("stop_strings", None), kwargs.pop("tokenizer", None) or None
@@ -422,6 +440,8 @@ class AfkGenerationMixin:
         lookup = _lookup.resolve(prompt_lookup_num_tokens, max_matching_ngram_size, gc, batch_size=input_ids.shape[0], do_sample=bool(do_sample), num_beams=int(num_beams),
                                  use_cache=bool(use_cache), exact_fp32=_exact.ENABLED, processors=spec.active or bool(procs), hooks=bool(criteria) or streamer is not None,
                                  stop_strings=bool(stop_spec.stop_strings), output_object=flags.return_dict)
+        # the shared prompt cache: keyword, else the class attribute; None: off or nothing to share, and nothing below changes
+        share = self._share_resolve(share_prompt, input_ids.shape[0], n_ret, int(num_beams), bool(use_cache), _exact.ENABLED, past is not None, hooks, lookup is not None, len(eos))
         if spec.active and (num_beams > 1 or not use_cache):
             raise AfkError("generate(repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens / sequence_bias / "
                            "bad_words_ids / min_length / forced_eos_token_id / exponential_decay_length_penalty): greedy or sampled decoding on the KV cache "
@@ -439,7 +459,7 @@ class AfkGenerationMixin:
             sampling = dict(temperature=float(temperature) if temperature else 1.0, top_k=int(top_k or 0), top_p=1.0 if top_p is None else float(top_p),
                             seed=(int(seed) if seed is not None else int(torch.seed())) & (2 ** 64 - 1), **warp)
         ids = input_ids.to(self.device_)
-        if n_ret > 1 and int(num_beams) == 1:   # sampled copies: GenerationMixin._expand_inputs_for_generation - every tensor input repeated row by row; the
+        if n_ret > 1 and int(num_beams) == 1 and share is None:   # sampled copies: GenerationMixin._expand_inputs_for_generation - every tensor input repeated row by row; the
             expand = lambda x: x.repeat_interleave(n_ret, dim=0) if torch.is_tensor(x) else x   # draw is keyed by (step, row), so the copies differ
             ids, input_features, input_features_mask, attention_mask = expand(ids), expand(input_features), expand(input_features_mask), expand(attention_mask)
         if not use_cache:
@@ -451,6 +471,8 @@ class AfkGenerationMixin:
         max_new = int(max_new_tokens)
         # a lookup step writes the cache slots of all its k + 1 rows; only the accepted ones ever become visible, so the cache needs k more positions
         headroom = max_new_tokens + (lookup.k if lookup else 0)
+        if share is not None:   # the prompt rows run once, into a cache that only ever holds the prompt: the generated positions go to the tail cache
+            headroom = 0
         cont = self._continue_from(past, attention_mask, B, S0, headroom) if past is not None else None   # (the caller's object, its AfkKVCache form, P)
         if cont is not None and cont[1] is not None:
             # a passed cache: only the suffix ids[:, P:] runs - its <sound> rows take the audio of THIS call - as n new rows behind P cached positions, on the
@@ -470,9 +492,15 @@ class AfkGenerationMixin:
 
                 cont = (cont[0], AfkKVCache(Kc, Vt, lo, 0), 0)
         if num_beams > 1:
-            return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), max_new, eos, pad, float(length_penalty), early_stopping, num_return=n_ret, use_graph=use_graph)
+            return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), max_new, eos, pad, float(length_penalty), early_stopping, num_return=n_ret, use_graph=use_graph, share=share)
         first_logits = ops.gemm_nt(last, self.arena["lm_head.weight"].data).float()
         V = first_logits.shape[1]
+        shared = None
+        if share is not None:
+            # sampled copies on a shared prompt: the B prompt rows were prefilled once; from here on the call has B * n rows - the first logits and the id
+            # history the processors and the stop rule keep are repeated row by row, the cache the steps append to is the tail cache, slots from 0
+            shared, (Kc, Vt), lo, rep = self._share_setup(share, (Kc, Vt), lo, S0, max_new)
+            first_logits, ids, B = first_logits.index_select(0, rep).contiguous(), ids.index_select(0, rep).contiguous(), B * share.n
         if lookup is not None:
             return self._continue_done(cont, self._generate_lookup(ids, first_logits, (Kc, Vt), lo, lookup, max_new, eos, use_graph))
         rec = None
@@ -490,8 +518,8 @@ class AfkGenerationMixin:
             first_logits = procs(ids, first_logits)
         if not sampling:
             self._record_rows(rec, "scores", first_logits, step_off=0)
-        st = self._new_state((Kc, Vt), lo, S0, self._sample_token(first_logits, sampling, **self._scores_kw(rec)) if sampling else self._select_token(first_logits),
-                             sampling=sampling, tok_off=1 - S0, proc=proc, rec=rec)   # the first token is draw 0
+        st = self._new_state((Kc, Vt), lo, S0 if shared is None else 0, self._sample_token(first_logits, sampling, **self._scores_kw(rec)) if sampling else self._select_token(first_logits),
+                             sampling=sampling, tok_off=1 - S0 if shared is None else 1, proc=proc, rec=rec, shared=shared)   # the first token is draw 0
         stop = None
         if stop_spec.device:   # more than one eos id, or stop strings: the rule is a launch of the step.  Token 0, eagerly, with the kernel of the captured steps
             stop = st.stop = _stop.build_state(stop_spec, ids, max_new, _stop.build_table(tokenizer, stop_spec.stop_strings) if stop_spec.stop_strings else None)
@@ -527,7 +555,25 @@ class AfkGenerationMixin:
             if eos1 is not None:  # everything after a row's first EOS becomes padding (GenerationMixin semantics)
                 after = (new == eos1).cumsum(1) - (new == eos1).long() > 0
                 new = torch.where(after, torch.full_like(new, pad), new)
-        return self._continue_done(cont, self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st.cache, lo))
+        return self._continue_done(cont, self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st.cache, lo, shared=shared))
+
+    def _share_resolve(self, share_prompt, B0, copies, num_beams, use_cache, exact_fp32, past, hooks, lookup, n_eos):
+        """decode_share.resolve with what only the model knows: whether the device beam step takes the call, whether B0 * n rows take the batched decode chain
+        and the geometry lies inside afk_attn_decode_shared's envelope"""
+        n = num_beams if num_beams > 1 else copies
+        on = self.share_prompt_cache if share_prompt is None else share_prompt
+        geometry = beam_device = True
+        if on and n > 1:   # asked only where the answer is read: with the switch off the call reads no weight and no attribute it did not read before
+            geometry = ops.attn_shared_supported(self.Hq, self.Hkv, self.D, n) and self._chain_batched_ok(B0 * n, self.arena["lm_head.weight"].data)
+            beam_device = self.beam_on_device and ops.beam_caps_ok(num_beams, n_eos, self.V)
+        return _share.resolve(share_prompt, self.share_prompt_cache, copies=copies, num_beams=num_beams, use_cache=use_cache, exact_fp32=exact_fp32, past=past,
+                              hooks=hooks, lookup=lookup, beam_device=beam_device, geometry=geometry)
+
+    def _share_setup(self, share, prompt_cache, lo, S0, max_new):
+        """decode_share.build behind the prefill, and the call's last_share_stats -> (SharedPrompt, the tail cache, lo per continuation, rep)"""
+        shared, tail, lo_rep, rep = _share.build(share, prompt_cache, lo, S0, max_new, self.Hq, self.Hkv, self.D)
+        self.last_share_stats = _share.stats(shared, tail, max_new)
+        return shared, tail, lo_rep, rep
 
     def _continue_from(self, past, attention_mask, B, S_total, headroom):
         """generate(past_key_values=past) -> (the caller's object, the AfkKVCache the call works on, P).  An AfkKVCache is worked on directly; the reference's
@@ -596,9 +642,10 @@ class AfkGenerationMixin:
         return torch.cat([ids, ls["tokens"][None, :st[_lookup.EMITTED]]], dim=1)
 
     @staticmethod
-    def _generate_output(flags, sequences, S0, rec, cache, lo):
+    def _generate_output(flags, sequences, S0, rec, cache, lo, shared=None):
         """what generate() returns: the plain sequences, or under return_dict_in_generate the AfkGenerateOutput around them - n = generated columns, scores /
-        logits = the first n slots of the recorded buffers as tuples of [B, V] views, past_key_values = the cache of every token but the last"""
+        logits = the first n slots of the recorded buffers as tuples of [B, V] views, past_key_values = the cache of every token but the last (shared: `cache` is
+        the tail cache and lo is per continuation - the two caches are laid out as one plain cache of B * n rows, decode_share.materialize)"""
         if not flags.return_dict:
             return sequences
         from .generation_output import AfkGenerateOutput
@@ -608,7 +655,11 @@ class AfkGenerationMixin:
         rows = lambda k: tuple(rec[k][i] for i in range(n)) if rec and rec.get(k) is not None else None
         logits = rows("logits")
         scores = logits if (rec and rec.get("scores") is not None and rec["scores"] is rec.get("logits")) else rows("scores")   # the same tensor objects, as the reference
-        return AfkGenerateOutput(sequences=sequences, scores=scores, logits=logits, past_key_values=AfkKVCache(cache[0], cache[1], lo, S0 + n - 1))
+        if shared is not None:
+            kv = _share.materialize(shared.cache[0], shared.cache[1], lo[::shared.n], S0, cache[0], cache[1], shared.n, S0 + n - 1)
+        else:
+            kv = AfkKVCache(cache[0], cache[1], lo, S0 + n - 1)
+        return AfkGenerateOutput(sequences=sequences, scores=scores, logits=logits, past_key_values=kv)
 
     def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits=False):
         """GenerationMixin.compute_transition_scores (transformers/generation/utils.py:1433-1555) for greedy / sampled outputs: [B, len(scores)] fp32, the

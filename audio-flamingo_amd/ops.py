@@ -768,6 +768,78 @@ def attn_append(q, Kc, Vt, krange, B, n, Hq, Hkv, D, scale, nsplit=None, ws=None
     return o
 
 
+ATTN_SHARED_MAX_SPLITS = 64      # afk_attn_decode_shared refuses more (csrc/attention_shared.hip SHARED_MAX_SPLITS)
+ATTN_SHARED_MAX_COPIES = 16      # continuations per prompt row (SHARED_MAX_COPIES)
+ATTN_SHARED_TARGET_BLOCKS = 256  # one block per CU, attn_append_nsplit's target: the prompt blocks have the append kernel's shape
+ATTN_SHARED_MIN_CHUNK = 128      # keys: no prompt chunk shorter than this
+ATTN_SHARED_RULE_SPLITS = 16     # most splits the rule asks for
+
+
+def attn_shared_supported(Hq, Hkv, D, n):
+    """the geometries and copy counts afk_attn_decode_shared takes"""
+    return attn_append_supported(Hq, Hkv, D) and 1 <= int(n) <= ATTN_SHARED_MAX_COPIES
+
+
+def attn_shared_nsplit(B0, n, Hq, Hkv, keys):
+    """prompt key splits of afk_attn_decode_shared from the shape alone (no device read), modelled on attn_append_nsplit: the launch has B0 * Hkv *
+    ceil(n / copies per tile) prompt tiles; split until ATTN_SHARED_TARGET_BLOCKS blocks exist, but never into chunks shorter than ATTN_SHARED_MIN_CHUNK of
+    the `keys` prompt positions, and never more than ATTN_SHARED_RULE_SPLITS (the kernel itself takes up to ATTN_SHARED_MAX_SPLITS).  Always >= 1."""
+    tiles = max(1, int(B0) * int(Hkv) * -(-max(int(n), 1) // (32 // max(Hq // Hkv, 1))))
+    ns = -(-ATTN_SHARED_TARGET_BLOCKS // tiles)
+    return max(1, min(ns, max(int(keys), 0) // ATTN_SHARED_MIN_CHUNK, ATTN_SHARED_RULE_SPLITS))
+
+
+def attn_shared_check(Kp, Vtp, Kt, Vtt, prange, trange, B0, n, Hkv, D):
+    """the shape and stride checks of attn_decode_shared on what stays the same from step to step: one layer of the prompt cache and of the tail cache, and
+    the two interval tensors (a decode loop checks them once and then calls afk_attn_decode_shared itself)"""
+    R = int(B0) * int(n)
+    for t_, name in ((Kp, "Kp"), (Vtp, "Vtp"), (Kt, "Kt"), (Vtt, "Vtt")):
+        _chk(t_, BF16, name)
+    _chk(prange, torch.int32, "prange"), _chk(trange, torch.int32, "trange")
+    for K_, V_, rows, kn, vn in ((Kp, Vtp, B0, "Kp", "Vtp"), (Kt, Vtt, R, "Kt", "Vtt")):
+        if K_.dim() != 3 or tuple(K_.shape) != (rows, K_.shape[1], Hkv * D) or K_.stride(2) != 1:
+            raise AfkError(f"attn_decode_shared: {kn} {tuple(K_.shape)} strides {K_.stride()} is not [{rows}, positions, Hkv*D = {Hkv * D}] with unit column stride")
+        if (V_.dim() != 4 or tuple(V_.shape) != (rows, Hkv, D, V_.shape[3]) or V_.shape[3] < K_.shape[1]
+                or (V_.numel() and V_.stride()[1:] != (D * V_.shape[3], V_.shape[3], 1))):   # a cache of no positions has no strides to speak of
+            raise AfkError(f"attn_decode_shared: {vn} {tuple(V_.shape)} strides {V_.stride()} is not [{rows}, Hkv = {Hkv}, D = {D}, spad >= {K_.shape[1]}] with its "
+                           f"heads and features contiguous")
+    if tuple(prange.shape) != (B0, 2) or not prange.is_contiguous() or tuple(trange.shape) != (R, 2) or not trange.is_contiguous():
+        raise AfkError(f"attn_decode_shared: prange {tuple(prange.shape)} / trange {tuple(trange.shape)} are not contiguous [B0 = {B0}, 2] / [B0*n = {R}, 2]")
+
+
+def attn_decode_shared(q, Kp, Vtp, Kt, Vtt, prange, trange, B0, n, Hq, Hkv, D, scale, nsplit=None, ws=None, out=None):
+    """shared-prompt decode attention (afk_attn_decode_shared): one query row per continuation r = b0 * n + c over the prompt keys of row b0 and its own tail
+    keys, two launches.  q [B0*n, >= Hq*D] row-strided view (post-RoPE); Kp [B0, Sp, Hkv*D], Vtp [B0, Hkv, D, spad_p] (one layer of the prompt cache);
+    Kt [B0*n, T, Hkv*D], Vtt [B0*n, Hkv, D, spad_t] (one layer of the tail cache); prange [B0, 2] / trange [B0*n, 2] int32 on the device: the visible
+    intervals.  nsplit None: attn_shared_nsplit over the prompt rows.  ws: a float32 workspace of at least afk_attn_decode_shared_workspace_floats(B0, n, Hq, D,
+    nsplit) elements (None: allocated here).  -> o [B0*n, Hq*D] bf16"""
+    B0, n = int(B0), int(n)
+    R = B0 * n
+    _chk(q, BF16, "q")
+    if q.dim() != 2 or q.shape[0] != R or q.shape[1] < Hq * D or q.stride(1) != 1:
+        raise AfkError(f"attn_decode_shared: q {tuple(q.shape)} strides {q.stride()} is not [B0*n = {R}, >= Hq*D = {Hq * D}] with unit column stride")
+    attn_shared_check(Kp, Vtp, Kt, Vtt, prange, trange, B0, n, Hkv, D)
+    Sp, T = Kp.shape[1], Kt.shape[1]
+    ns = attn_shared_nsplit(B0, n, Hq, Hkv, Sp) if nsplit is None else int(nsplit)
+    if ws is None:
+        ws = torch.empty(int(_lib.load().afk_attn_decode_shared_workspace_floats(B0, max(min(n, ATTN_SHARED_MAX_COPIES), 1), Hq, D,
+                                                                                max(min(ns, ATTN_SHARED_MAX_SPLITS), 1))), device=q.device, dtype=torch.float32)
+    else:
+        _chk(ws, torch.float32, "ws")
+    if out is None:
+        o = torch.empty((R, Hq * D), device=q.device, dtype=BF16)
+    else:
+        o = _chk(out, BF16, "out")
+        if tuple(o.shape) != (R, Hq * D) or o.stride(1) != 1:
+            raise AfkError(f"attn_decode_shared: out {tuple(o.shape)} strides {o.stride()} is not [B0*n, Hq*D] with unit column stride")
+    # the strides are the tensors' own: a cache view with a longer row or sample pitch is read as it lies; a cache of no positions is never dereferenced
+    kp, vp, kt, vt = ((t_.data_ptr() if t_.numel() else None) for t_ in (Kp, Vtp, Kt, Vtt))
+    _lib.call("afk_attn_decode_shared", q.data_ptr(), q.stride(0), D, kp, Kp.stride(0), Kp.stride(1), D, vp, Vtp.stride(0), Vtp.shape[3], Sp,
+              kt, Kt.stride(0), Kt.stride(1), D, vt, Vtt.stride(0), Vtt.shape[3], T, o.data_ptr(), o.stride(0), D, prange.data_ptr(), trange.data_ptr(),
+              B0, n, Hq, Hkv, D, float(scale), ns, ws.data_ptr(), ws.numel(), _stream())
+    return o
+
+
 def attn_interval_fwd(qkv, krange, B, S, Hq, Hkv, D, *, scale):
     """self-attention on a fused q|k|v projection with a per-query key interval (left / right / both-side padding, causal or not)"""
     _chk(qkv, BF16, "qkv")

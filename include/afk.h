@@ -362,6 +362,28 @@ int afk_attn_append(const void* Q, int64_t q_bs, int64_t q_hs, int64_t q_rs, con
                     const void* Vt, int64_t vt_bs, int spad, void* O, int64_t o_bs, int64_t o_hs, int64_t o_rs, const int* krange, int B,
                     int Hq, int Hkv, int n, int D, float scale, int nsplit, float* ws, int64_t ws_floats, void* stream);
 
+/* Shared-prompt decode attention (csrc/attention_shared.hip): ONE query row per continuation, n continuations (sampled copies, beams) per prompt row, the prompt
+ * keys stored once per prompt row.  Continuation r = b0 * n + c (copy c of prompt row b0) attends to the UNION of
+ *   the prompt keys [prange[b0][0], prange[b0][1]) of row b0 of the prompt cache: Kp [B0][Sp][Hkv][D] (kp_bs, kp_rs, kp_hs), V^T Vtp [B0][Hkv][D][spad_p] (vtp_bs), and
+ *   the tail keys   [trange[r][0],  trange[r][1])  of row r of the tail cache:    Kt [B0*n][T][Hkv][D] (kt_bs, kt_rs, kt_hs), V^T Vtt [B0*n][Hkv][D][spad_t] (vtt_bs)
+ * - both one layer of an AfkKVCache as afk_kv_cache_append writes it.  Q [B0*n][Hq][D] by strides (q_rs per continuation, q_hs per head), O likewise (o_rs, o_hs);
+ * bf16 in and out, fp32 scores, softmax and accumulation, probabilities rounded to bf16 in front of P.V (afk_attn_append's arithmetic).  prange [B0][2] and
+ * trange [B0*n][2] are int32 in DEVICE memory, read by the kernel (capturable); interval ends are clamped into [0, Sp] / [0, T].  A continuation that sees no key
+ * at all is a zero row (+0.0, the bits afk_attn_append writes).  Two plain launches: partials - a block per (prompt row, KV head, tile of 32 / (Hq / Hkv) copies,
+ * prompt key split) serves every copy of the tile from ONE fetch of a prompt key row, a block per (continuation, KV head) takes its tail - then the merge of the
+ * nsplit prompt parts and the tail part in that order.  No counters, no atomics, no cross-block waits: the result depends on the inputs and nsplit alone.
+ * What may hold anything, NaN included: every cache slot and V^T column outside the two intervals (slots behind the last key, tail slots not yet written, in front
+ * of a left-padded row's first key, the pad columns of V^T); they are neither multiplied nor, for key rows, read.
+ * head_dim 64 / 128; Hq / Hkv in {1, 2, 4, 7, 8}; 1 <= n <= 16; 1 <= nsplit <= 64 (the prompt interval is cut into nsplit chunks on 32-key boundaries);
+ * spad_p >= Sp and spad_t >= T, both multiples of 32 (0 with a cache of no positions, whose pointers may then be NULL); element strides of Q / O / K % 8 == 0, of
+ * V^T % 4 == 0; ceil(n / copies per tile) * Hkv <= 65 535, B0 <= 65 535.  ws: ws_floats >= afk_attn_decode_shared_workspace_floats(B0, n, Hq, D, nsplit) floats,
+ * 16-byte aligned, no initial contents required.  Everything else is refused with AFK_ERR_ARG. */
+int64_t afk_attn_decode_shared_workspace_floats(int B0, int n, int Hq, int D, int nsplit);
+int afk_attn_decode_shared(const void* Q, int64_t q_rs, int64_t q_hs, const void* Kp, int64_t kp_bs, int64_t kp_rs, int64_t kp_hs, const void* Vtp,
+                           int64_t vtp_bs, int spad_p, int Sp, const void* Kt, int64_t kt_bs, int64_t kt_rs, int64_t kt_hs, const void* Vtt,
+                           int64_t vtt_bs, int spad_t, int T, void* O, int64_t o_rs, int64_t o_hs, const int* prange, const int* trange, int B0, int n,
+                           int Hq, int Hkv, int D, float scale, int nsplit, float* ws, int64_t ws_floats, void* stream);
+
 /* Decode-step glue (csrc/decode_glue.hip): the weight-streaming first pass alone, and one kernel per Linear of a decoder layer that sums
  * its fp32 partials ws[splits][M][N] and applies everything up to the next Linear's input (one live row per call today: M <= AFK_GEMV_MAX_M; same arithmetic and bf16
  * rounding points as the stand-alone kernels; oracle lines: modeling_qwen2.py:46-48, 112-135, 213-214, 247-252, 284-297). */
