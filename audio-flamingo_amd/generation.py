@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib, ops
+from . import decode_cfg as _cfg
 from . import decode_lookup as _lookup
 from . import decode_process as _process
 from . import decode_share as _share
@@ -57,6 +58,7 @@ class DecodeState:
     single: Optional[SingleSequence] = None
     on_device: Optional[OnDevice] = None
     shared: Optional[_share.SharedPrompt] = None   # the prompt cache of a call that shares it (decode_share.py): `cache` is then the TAIL cache, cur counts its slots from 0
+    cfg: Optional[_cfg.CfgState] = None   # classifier-free guidance (decode_cfg.py): cache, lo and nxt have 2 * B rows - [0, B) conditional, [B, 2B) unconditional - and everything else B
 
 
 def _run_steps(step, max_new, use_graph, closed, after=None):
@@ -115,6 +117,7 @@ class AfkGenerationMixin:
     lookup_on_device = os.environ.get("AFK_LOOKUP_DEVICE", "1") == "1"   # prompt-lookup decoding: the draft and accept rules as launches of the step (csrc/decode_lookup.hip); off: torch ops and host reads
     share_prompt_cache = os.environ.get("AFK_SHARE_PROMPT", "0") == "1"   # generate(share_prompt=None): sampled copies and device beams share the prompt's keys (decode_share.py, csrc/attention_shared.hip)
     last_share_stats = None   # the last generate() call that shared a prompt cache: decode_share.stats; None after every other call
+    last_cfg_stats = None   # the last generate() call under classifier-free guidance: decode_cfg.stats; None after every other call
 
     # ------------------------------------------------------------------ the pieces of a step
     @staticmethod
@@ -165,12 +168,25 @@ class AfkGenerationMixin:
                                  min_p=sampling["min_p"], typical_p=sampling["typical_p"], epsilon_cutoff=sampling["epsilon_cutoff"],
                                  eta_cutoff=sampling["eta_cutoff"], **kw)
 
-    def _record_and_process(self, st, logits, *, step_base=None, step_off=0, **select):
+    @staticmethod
+    def _guided_rows(st, logits):
+        """the rows of a step's logits the selection works on, their unconditional partners and the tokens' place in st.nxt: everything as it is without
+        guidance; under it (st.cfg) logits is [2 * B, V] and the three are views - rows [0, B), rows [B, 2B), nxt[:B].  Host code only."""
+        if st.cfg is None:
+            return logits, None, st.nxt
+        B = st.cfg.B
+        return logits[:B], logits[B:], st.nxt[:B]
+
+    def _record_and_process(self, st, logits, *, step_base=None, step_off=0, uncond=None, **select):
         """the front of every route's token: the raw row recorded in front of the processors, then the built-in processors in place (`select`: the launch
-        also selects greedily from the row it leaves and does the step's bookkeeping, ops.decode_process)"""
+        also selects greedily from the row it leaves and does the step's bookkeeping, ops.decode_process).  uncond (classifier-free guidance: the unconditional
+        rows of the same step): between the two, afk_decode_cfg folds each pair into the conditional row, in place - stage 0 of the processor list, behind the
+        record, so `logits` keeps the raw conditional rows as the reference's raw_logits does"""
         self._record_rows(st.rec, "logits", logits, step_base=step_base, step_off=step_off)
+        if uncond is not None:
+            ops.decode_cfg(logits, uncond, st.cfg.scale, out=logits, ws=st.cfg.ws)
         if st.proc:   # the token being generated is number cur + 1 - S0: the processors' (and the draw's) counter lives on the device and advances with the step
-            _process.apply(st.proc, logits, next_token=st.nxt, step_base=step_base, step_off=step_off, **select)
+            _process.apply(st.proc, logits, next_token=st.nxt if st.cfg is None else st.nxt[:st.cfg.B], step_base=step_base, step_off=step_off, **select)
 
     def _pick_token(self, st, logits, *, step_base=None, step_off=0, record=True, out=None, **book):
         """the token of the processed rows, into `out` where given: the draw (whose launch keeps the warped row where scores were asked for; book: the
@@ -217,11 +233,13 @@ class AfkGenerationMixin:
             if st.stop:   # behind the selection launch, which has advanced cur (= state[2]) already: one step back.  The next embedding row is in x0: no pad is fed
                 _stop.apply(st.stop, st.nxt, step_base=st.cur, step_off=st.tok_off - 1)
             return
-        logits = self._decode_logits(st)
-        self._record_and_process(st, logits, step_base=st.cur, step_off=st.tok_off)
-        self._pick_token(st, logits, step_base=st.cur, step_off=st.tok_off, out=st.nxt)
+        logits, uncond, nxt = self._guided_rows(st, self._decode_logits(st))
+        self._record_and_process(st, logits, step_base=st.cur, step_off=st.tok_off, uncond=uncond)
+        self._pick_token(st, logits, step_base=st.cur, step_off=st.tok_off, out=nxt)
         if st.stop:   # the stopping rule on the token just selected; a row that finished earlier emits pad_token_id and the next step embeds it
-            _stop.apply(st.stop, st.nxt, step_base=st.cur, step_off=st.tok_off, feed_pad=True)
+            _stop.apply(st.stop, nxt, step_base=st.cur, step_off=st.tok_off, feed_pad=True)
+        if uncond is not None:   # the unconditional row of a pair is fed the token of its conditional row (pad behind the row's end): one small copy
+            st.nxt[st.cfg.B:].copy_(nxt)
         (st.single.advance if st.single is not None else st.cur).add_(1)   # single sequence: cur, position and the key-range end live in one tensor
 
     def _new_state(self, cache, lo, cur, nxt, **kw):
@@ -350,7 +368,8 @@ class AfkGenerationMixin:
                  use_graph=None, num_beams=1, length_penalty=1.0, early_stopping=False, generation_config=None, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, min_p=None, typical_p=1.0,
                  epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, sequence_bias=None, bad_words_ids=None, min_length=0,
-                 forced_eos_token_id=None, exponential_decay_length_penalty=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, share_prompt=None, **kwargs):
+                 forced_eos_token_id=None, exponential_decay_length_penalty=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, share_prompt=None,
+                 guidance_scale=None, negative_prompt_ids=None, negative_prompt_attention_mask=None, **kwargs):
         """Greedy decoding, sampling or beam search on a KV cache, with GenerationMixin.generate's arguments and results; docs/generate.md describes every
         route, what it launches and how it differs from the reference.
 
@@ -381,6 +400,12 @@ class AfkGenerationMixin:
         num_return_sequences = n) or the device beams of a row share ONE prefill and ONE copy of the prompt's keys; a step attends to the prompt cache and
         a short tail cache of generated positions (afk_attn_decode_shared).  False, or nothing to share: not one launch or allocation differs.  The ids can
         differ from the unshared call on near-ties (the prefill runs on other row counts); docs/generate.md, "Sharing the prompt".
+        guidance_scale (None; keyword, else the generation config) with negative_prompt_ids [B, Sn] (None: the last id of every prompt row) and
+        negative_prompt_attention_mask (LEFT padding): classifier-free guidance, the reference's UnbatchedClassifierFreeGuidanceLogitsProcessor - active for
+        any scale but None and 1 (inactive: the negative prompt is ignored, and not one launch or allocation differs).  Every prompt row gets an unconditional
+        row (the negative prompt, text only, its own cache rows, the same selected tokens) in the same decode step - one pass over the weights for both -
+        and afk_decode_cfg replaces the row's logits by scale * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond) in front of every
+        processor; `logits` keeps the raw conditional rows, past_key_values the conditional cache.  docs/generate.md, "Classifier-free guidance".
         generation_config (default: self.generation_config if there is one) supplies every argument left at its default.
 
         Returns the ids [B * num_return_sequences, S0 + n]: the prompt, then the new tokens, pad_token_id behind a row's end.
@@ -393,9 +418,11 @@ class AfkGenerationMixin:
         output_attentions / output_hidden_states; past_key_values with num_beams > 1, use_cache=False, AFK_EXACT_FP32=1 or num_return_sequences > 1, with an
         attention mask that has holes (AfkError), or with a cache that is not shorter than input_ids (ValueError naming both lengths); share_prompt=True
         with use_cache=False, AFK_EXACT_FP32=1, past_key_values, the per-step hooks, prompt-lookup decoding, the host beam loop or a geometry outside the
-        batched decode chain (decode_share.resolve)."""
+        batched decode chain (decode_share.resolve); guidance_scale with num_beams > 1, use_cache=False, AFK_EXACT_FP32=1, prompt-lookup decoding,
+        past_key_values or share_prompt=True, with a negative prompt that holds the audio id or a negative mask that is not left padding (AfkError), with
+        negative_prompt_ids of another batch size or a mask of another shape (ValueError) (decode_cfg.resolve)."""
         self._require_hip()
-        self.last_share_stats = None
+        self.last_share_stats = self.last_cfg_stats = None
         procs, criteria, streamer = kwargs.pop("logits_processor", None), kwargs.pop("stopping_criteria", None), kwargs.pop("streamer", None)
         out_kw = {k: kwargs.pop(k, None) for k in ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")}
         stop_strings, tokenizer = kwargs.pop("stop_strings", None), kwargs.pop("tokenizer", None) or None
@@ -436,6 +463,13 @@ class AfkGenerationMixin:
                                f"the KV cache only")
         if int(max_new_tokens) <= 0:   # GenerationMixin refuses it as well (generation/configuration_utils.py validate())
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
+        # classifier-free guidance: keyword, else generation config, with every refusal; None: inactive (no scale, or 1), and nothing below changes
+        cfg = _cfg.resolve(guidance_scale, negative_prompt_ids, negative_prompt_attention_mask, gc, batch_size=input_ids.shape[0],
+                           audio_token_id=getattr(self, "audio_token_id", None), num_beams=int(num_beams), use_cache=bool(use_cache), exact_fp32=_exact.ENABLED,
+                           lookup=prompt_lookup_num_tokens is not None or getattr(gc, "prompt_lookup_num_tokens", None) is not None, past=past is not None,
+                           share_prompt=share_prompt)
+        if cfg is not None and share_prompt is None:
+            share_prompt = False   # the class attribute on: a guided call takes the unshared route, silently
         # prompt-lookup decoding: keyword, else generation config; None: off, and nothing below changes
         lookup = _lookup.resolve(prompt_lookup_num_tokens, max_matching_ngram_size, gc, batch_size=input_ids.shape[0], do_sample=bool(do_sample), num_beams=int(num_beams),
                                  use_cache=bool(use_cache), exact_fp32=_exact.ENABLED, processors=spec.active or bool(procs), hooks=bool(criteria) or streamer is not None,
@@ -462,6 +496,8 @@ class AfkGenerationMixin:
         if n_ret > 1 and int(num_beams) == 1 and share is None:   # sampled copies: GenerationMixin._expand_inputs_for_generation - every tensor input repeated row by row; the
             expand = lambda x: x.repeat_interleave(n_ret, dim=0) if torch.is_tensor(x) else x   # draw is keyed by (step, row), so the copies differ
             ids, input_features, input_features_mask, attention_mask = expand(ids), expand(input_features), expand(input_features_mask), expand(attention_mask)
+            if cfg is not None:   # the negative prompt and its mask like the other inputs
+                cfg = cfg._replace(negative_ids=expand(cfg.negative_ids), negative_mask=expand(cfg.negative_mask))
         if not use_cache:
             if do_sample:
                 raise AfkError("generate(use_cache=False) is the greedy reference path of the tests")
@@ -471,8 +507,8 @@ class AfkGenerationMixin:
         max_new = int(max_new_tokens)
         # a lookup step writes the cache slots of all its k + 1 rows; only the accepted ones ever become visible, so the cache needs k more positions
         headroom = max_new_tokens + (lookup.k if lookup else 0)
-        if share is not None:   # the prompt rows run once, into a cache that only ever holds the prompt: the generated positions go to the tail cache
-            headroom = 0
+        if share is not None or cfg is not None:   # the prompt rows run once, into a cache that only ever holds the prompt: the generated positions go to the tail
+            headroom = 0                           # cache (sharing) or to the combined cache of both branches (guidance)
         cont = self._continue_from(past, attention_mask, B, S0, headroom) if past is not None else None   # (the caller's object, its AfkKVCache form, P)
         if cont is not None and cont[1] is not None:
             # a passed cache: only the suffix ids[:, P:] runs - its <sound> rows take the audio of THIS call - as n new rows behind P cached positions, on the
@@ -501,6 +537,11 @@ class AfkGenerationMixin:
             # history the processors and the stop rule keep are repeated row by row, the cache the steps append to is the tail cache, slots from 0
             shared, (Kc, Vt), lo, rep = self._share_setup(share, (Kc, Vt), lo, S0, max_new)
             first_logits, ids, B = first_logits.index_select(0, rep).contiguous(), ids.index_select(0, rep).contiguous(), B * share.n
+        guide = uncond_first = None
+        if cfg is not None:
+            # classifier-free guidance: the unconditional rows are prefilled on their own (text only, their own length) and both prompts move into ONE cache of
+            # 2 * B rows, aligned to the right at slot Smax; from here on lo has 2 * B entries and the steps append at Smax, Smax + 1, ...
+            guide, (Kc, Vt), lo, uncond_first = self._cfg_setup(cfg, ids, (Kc, Vt), lo, S0, max_new, V)
         if lookup is not None:
             return self._continue_done(cont, self._generate_lookup(ids, first_logits, (Kc, Vt), lo, lookup, max_new, eos, use_graph))
         rec = None
@@ -508,8 +549,10 @@ class AfkGenerationMixin:
             new_buf = lambda: torch.empty((max_new, B, V), device=dev, dtype=torch.float32)
             rec = {"logits": new_buf() if flags.logits else None, "scores": None}
             if flags.scores:   # greedy with no processor of any kind: the reference returns the same tensors in both tuples - one buffer, one record per step
-                rec["scores"] = rec["logits"] if (flags.logits and not sampling and not spec.active and not procs) else new_buf()
+                rec["scores"] = rec["logits"] if (flags.logits and not sampling and not spec.active and not procs and guide is None) else new_buf()
             self._record_rows(rec, "logits", first_logits, step_off=0)   # token 0, eagerly, with the kernel of the captured steps
+        if guide is not None:   # token 0, eagerly, with the kernel of the captured steps: behind the record of the raw row, in front of every processor
+            ops.decode_cfg(first_logits, uncond_first, guide.scale, out=first_logits, ws=guide.ws)
         proc = None
         if spec.active:   # token 0, eagerly, with the kernel of the captured steps; in front of the user's processors (GenerationMixin._merge_criteria_processor_list)
             proc = _process.build_state(spec, ids, max_new, V)
@@ -518,13 +561,17 @@ class AfkGenerationMixin:
             first_logits = procs(ids, first_logits)
         if not sampling:
             self._record_rows(rec, "scores", first_logits, step_off=0)
-        st = self._new_state((Kc, Vt), lo, S0 if shared is None else 0, self._sample_token(first_logits, sampling, **self._scores_kw(rec)) if sampling else self._select_token(first_logits),
-                             sampling=sampling, tok_off=1 - S0 if shared is None else 1, proc=proc, rec=rec, shared=shared)   # the first token is draw 0
+        tok0 = self._sample_token(first_logits, sampling, **self._scores_kw(rec)) if sampling else self._select_token(first_logits)
+        cur0 = S0 if shared is None else 0   # the cache slot the first step appends at; the token it selects is number cur + tok_off
+        if guide is not None:   # both rows of a pair are fed the token; the slots count from where both prompts end
+            tok0, cur0 = torch.cat([tok0, tok0]), guide.Smax
+        st = self._new_state((Kc, Vt), lo, cur0, tok0, sampling=sampling, tok_off=1 - cur0, proc=proc, rec=rec, shared=shared, cfg=guide)   # the first token is draw 0
+        sel = (lambda: st.nxt) if guide is None else (lambda: st.nxt[:B])   # the tokens of the B selected rows
         stop = None
         if stop_spec.device:   # more than one eos id, or stop strings: the rule is a launch of the step.  Token 0, eagerly, with the kernel of the captured steps
             stop = st.stop = _stop.build_state(stop_spec, ids, max_new, _stop.build_table(tokenizer, stop_spec.stop_strings) if stop_spec.stop_strings else None)
-            _stop.apply(stop, st.nxt, step_off=0)
-        if B == 1:   # one device tensor [lo, key-range end, cache slot, position] -> the views the kernels read; one add per step moves the last three
+            _stop.apply(stop, sel(), step_off=0)
+        if B == 1 and guide is None:   # (guidance: two cache rows, the batched route) one device tensor [lo, key-range end, cache slot, position] -> the views the kernels read; one add per step moves the last three
             state = torch.cat([lo, torch.tensor([S0 + 1, S0], device=dev, dtype=torch.int32), S0 - lo]).contiguous()
             st.cur, st.single = state[2:3], SingleSequence(state=state, kr1=state[0:2], pos1=state[3:4], advance=state[1:4])
             if not hooks and self._chain_ok(1) and V % 8 == 0:   # token selection (argmax or the draw) and step bookkeeping stay on the device
@@ -538,15 +585,15 @@ class AfkGenerationMixin:
                     od.part_val, od.part_idx = torch.empty(V // 8, device=dev, dtype=torch.float32), torch.empty(V // 8, device=dev, dtype=torch.int32)
         if hooks:
             seq = self._generate_with_hooks(ids, st, first_logits, max_new, procs, criteria, streamer, eos, pad)
-            return self._continue_done(cont, self._generate_output(flags, seq, S0, rec, st.cache, lo))
+            return self._continue_done(cont, self._generate_output(flags, seq, S0, rec, st.cache, lo, cfg=guide))
         od = st.on_device
-        toks = [st.nxt.clone()]
+        toks = [sel().clone()]
         eos1 = eos[0] if eos else None   # the scalar route (one eos id, no stop string): token buffers compared on the host, no stop launch
         if stop is not None:
             closed = lambda t: stop["status"].tolist()[1] == 0   # the poll keeps its cadence: one small copy, {last step, rows still open}
         else:
             closed = lambda t: eos1 is not None and bool(((od.tok_buf[None, :t] if od is not None else torch.stack(toks, 1)) == eos1).any(1).all())
-        n_new = 1 + _run_steps(lambda: self._decode_step(st), max_new, use_graph, closed, after=None if od is not None else lambda: toks.append(st.nxt.clone()))
+        n_new = 1 + _run_steps(lambda: self._decode_step(st), max_new, use_graph, closed, after=None if od is not None else lambda: toks.append(sel().clone()))
         if stop is not None:   # the reference's shape and padding: up to the step at which the last row finished; later steps only touched slots beyond it
             n_new = min(n_new, min(int(stop["stop_at"].max()), max_new) + 1)
             new = stop["ids"][:, S0:S0 + n_new].to(torch.int64)
@@ -555,7 +602,7 @@ class AfkGenerationMixin:
             if eos1 is not None:  # everything after a row's first EOS becomes padding (GenerationMixin semantics)
                 after = (new == eos1).cumsum(1) - (new == eos1).long() > 0
                 new = torch.where(after, torch.full_like(new, pad), new)
-        return self._continue_done(cont, self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st.cache, lo, shared=shared))
+        return self._continue_done(cont, self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st.cache, lo, shared=shared, cfg=guide))
 
     def _share_resolve(self, share_prompt, B0, copies, num_beams, use_cache, exact_fp32, past, hooks, lookup, n_eos):
         """decode_share.resolve with what only the model knows: whether the device beam step takes the call, whether B0 * n rows take the batched decode chain
@@ -568,6 +615,21 @@ class AfkGenerationMixin:
             beam_device = self.beam_on_device and ops.beam_caps_ok(num_beams, n_eos, self.V)
         return _share.resolve(share_prompt, self.share_prompt_cache, copies=copies, num_beams=num_beams, use_cache=use_cache, exact_fp32=exact_fp32, past=past,
                               hooks=hooks, lookup=lookup, beam_device=beam_device, geometry=geometry)
+
+    def _cfg_setup(self, cfg, ids, cond_cache, lo, S0, max_new, V):
+        """the unconditional branch of a guided call behind the main prefill (UnbatchedClassifierFreeGuidanceLogitsProcessor.get_unconditional_logits'
+        first pass, logits_process.py:2294-2312): its prompt is cfg.negative_ids [B, Sn] - None: the last id of every prompt row - with no audio, prefilled by
+        the ordinary set-up into a cache of its own; then decode_cfg.build lays both prompts into the combined cache, and the call's last_cfg_stats
+        -> (CfgState, the combined cache, lo [2 * B], the unconditional first logits [B, V] fp32)"""
+        B = ids.shape[0]
+        neg = cfg.negative_ids.to(self.device_) if cfg.negative_ids is not None else ids[:, -1:].contiguous()
+        Sn = neg.shape[1]
+        lo_u, padded, Ku, Vu, pos_rows, krange, fast = self._prefill_setup(cfg.negative_mask, B, Sn, 0, "generate(negative_prompt_attention_mask=...)")
+        y = self._decode_layers(self._merged_embeddings(neg, None, None), B, Sn, 0, (Ku, Vu), pos_rows, krange, fast, kv_lo=lo_u if padded else None)
+        uncond_first = ops.gemm_nt(y.reshape(B, Sn, -1)[:, -1, :].contiguous(), self.arena["lm_head.weight"].data).float()
+        guide, cache, lo2 = _cfg.build(cfg.scale, cond_cache, lo, S0, (Ku, Vu), lo_u, Sn, max_new, V)
+        self.last_cfg_stats = _cfg.stats(guide, cache)
+        return guide, cache, lo2, uncond_first
 
     def _share_setup(self, share, prompt_cache, lo, S0, max_new):
         """decode_share.build behind the prefill, and the call's last_share_stats -> (SharedPrompt, the tail cache, lo per continuation, rep)"""
@@ -642,10 +704,11 @@ class AfkGenerationMixin:
         return torch.cat([ids, ls["tokens"][None, :st[_lookup.EMITTED]]], dim=1)
 
     @staticmethod
-    def _generate_output(flags, sequences, S0, rec, cache, lo, shared=None):
+    def _generate_output(flags, sequences, S0, rec, cache, lo, shared=None, cfg=None):
         """what generate() returns: the plain sequences, or under return_dict_in_generate the AfkGenerateOutput around them - n = generated columns, scores /
         logits = the first n slots of the recorded buffers as tuples of [B, V] views, past_key_values = the cache of every token but the last (shared: `cache` is
-        the tail cache and lo is per continuation - the two caches are laid out as one plain cache of B * n rows, decode_share.materialize)"""
+        the tail cache and lo is per continuation - the two caches are laid out as one plain cache of B * n rows, decode_share.materialize; cfg:
+        `cache` has 2 * B rows and the B conditional ones are copied out, decode_cfg.materialize)"""
         if not flags.return_dict:
             return sequences
         from .generation_output import AfkGenerateOutput
@@ -655,7 +718,9 @@ class AfkGenerationMixin:
         rows = lambda k: tuple(rec[k][i] for i in range(n)) if rec and rec.get(k) is not None else None
         logits = rows("logits")
         scores = logits if (rec and rec.get("scores") is not None and rec["scores"] is rec.get("logits")) else rows("scores")   # the same tensor objects, as the reference
-        if shared is not None:
+        if cfg is not None:   # the conditional rows alone, at the slots a plain call would hold them in (the reference returns the conditional cache)
+            kv = _cfg.materialize(cache[0], cache[1], lo, cfg, S0 + n - 1)
+        elif shared is not None:
             kv = _share.materialize(shared.cache[0], shared.cache[1], lo[::shared.n], S0, cache[0], cache[1], shared.n, S0 + n - 1)
         else:
             kv = AfkKVCache(cache[0], cache[1], lo, S0 + n - 1)
@@ -700,9 +765,9 @@ class AfkGenerationMixin:
             streamer.put(ids.cpu())
         for t in range(max_new):
             if t > 0:
-                logits = self._decode_logits(st)        # appends the K / V of st.nxt at the cache slot st.cur
+                logits, uncond, _ = self._guided_rows(st, self._decode_logits(st))        # appends the K / V of st.nxt at the cache slot st.cur
                 (st.single.advance if st.single is not None else st.cur).add_(1)
-                self._record_and_process(st, logits, step_off=t)   # the built-in processors first: st.nxt is token t - 1 as appended to seq (pad for a finished row)
+                self._record_and_process(st, logits, step_off=t, uncond=uncond)   # guidance, then the built-in processors: st.nxt is token t - 1 as appended to seq (pad for a finished row)
                 if procs:
                     logits = procs(seq, logits)
             # token 0 is drawn a second time here (generate() drew it for st.nxt): the same draw, the same scores row - which generate() has recorded where it is greedy
@@ -723,7 +788,7 @@ class AfkGenerationMixin:
                 done = done | (r.to(dev).reshape(-1).bool() if torch.is_tensor(r) else torch.full_like(done, bool(r)))
             if bool(done.all()):
                 break
-            st.nxt.copy_(tok)
+            st.nxt.copy_(tok if st.cfg is None else torch.cat([tok, tok]))   # guidance: both rows of a pair are fed the token (pad for a finished row)
         if streamer is not None:
             streamer.end()
         return seq

@@ -948,6 +948,42 @@ def decode_record(src, dst, *, step_base=None, step_off=0, n_steps=None):
     return dst
 
 
+def decode_cfg_workspace(B, V, device):
+    """the workspace of decode_cfg for B rows of V columns (afk_decode_cfg_workspace_floats): uninitialised fp32; a decode step allocates it once"""
+    return torch.empty(int(_lib.load().afk_decode_cfg_workspace_floats(int(B), int(V))), device=device, dtype=torch.float32)
+
+
+def decode_cfg(cond, uncond, scale, out=None, *, ws=None):
+    """classifier-free guidance on fp32 logits rows [B, V] in one call of two launches (afk_decode_cfg; the contract is in include/afk.h):
+    out = scale * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond), a NaN logit counting as -inf.  out: None (a new tensor), cond itself (in
+    place) or any other [B, V] fp32 tensor that overlaps neither input; rows need unit column stride only.  ws: decode_cfg_workspace(B, V) (None: allocated
+    here - a captured step passes its own).  -> out"""
+    _chk(cond, torch.float32, "decode_cfg cond"), _chk(uncond, torch.float32, "decode_cfg uncond")
+    if cond.dim() != 2 or cond.shape[0] < 1 or cond.shape[1] < 1:
+        raise AfkError(f"decode_cfg cond: [B >= 1, V >= 1], got {tuple(cond.shape)}")
+    B, V = cond.shape
+    if out is None:
+        out = torch.empty((B, V), device=cond.device, dtype=torch.float32)
+    _chk(out, torch.float32, "decode_cfg out")
+    for t_, name in ((cond, "cond"), (uncond, "uncond"), (out, "out")):
+        if tuple(t_.shape) != (B, V) or t_.stride(1) != 1 or (B > 1 and t_.stride(0) < V) or t_.device != cond.device:
+            raise AfkError(f"decode_cfg {name}: [{B}, {V}] on {cond.device} with unit column stride and non-overlapping rows, got {tuple(t_.shape)} strides "
+                           f"{t_.stride()} on {t_.device}")
+    span = lambda t_: (t_.data_ptr(), t_.data_ptr() + 4 * ((B - 1) * t_.stride(0) + V))
+    overlap = lambda a, b: span(a)[0] < span(b)[1] and span(b)[0] < span(a)[1]
+    if overlap(out, uncond) or (overlap(out, cond) and not (out.data_ptr() == cond.data_ptr() and (B == 1 or out.stride(0) == cond.stride(0)))):
+        raise AfkError("decode_cfg out: it may be cond itself (in place); it must not overlap uncond, or cond in any other way")
+    if ws is None:
+        ws = decode_cfg_workspace(B, V, cond.device)
+    _chk(ws, torch.float32, "decode_cfg ws")
+    if not ws.is_contiguous() or ws.device != cond.device:
+        raise AfkError(f"decode_cfg ws: a contiguous fp32 tensor on {cond.device} (decode_cfg_workspace), got strides {ws.stride()} on {ws.device}")
+    ld = lambda t_: t_.stride(0) if B > 1 else V
+    _lib.call("afk_decode_cfg", cond.data_ptr(), ld(cond), uncond.data_ptr(), ld(uncond), float(scale), out.data_ptr(), ld(out), B, V, ws.data_ptr(), ws.numel(),
+              _stream())
+    return out
+
+
 def transition_scores(scores, tokens, *, normalize=False, out=None):
     """out [B, T] fp32 = scores[t, b, tokens[b, t]] - (normalize: logsumexp of that row), scores [T, B, V] fp32 with unit column stride, tokens [B, T] int64
     (afk_transition_scores: GenerationMixin.compute_transition_scores without beam_indices).  The ids are validated on the host (one sync: a post-hoc call)."""

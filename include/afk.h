@@ -480,6 +480,20 @@ int afk_decode_record(const float* src, int64_t ld_src, int B, int V, float* dst
  * order whatever the shape.  -inf entries contribute 0; a row with no finite entry answers NaN under normalize, as log_softmax does. */
 int afk_transition_scores(const float* scores, int64_t step_stride, int64_t ld, int T, int B, int V, const int64_t* tokens, int64_t ld_tokens, int normalize,
                           float* out, int64_t ld_out, void* stream);
+/* Classifier-free guidance inside the decode step (csrc/decode_cfg.hip; generate(guidance_scale=...); UnbatchedClassifierFreeGuidanceLogitsProcessor.__call__,
+ * transformers/generation/logits_process.py:2330-2339): for b < B, i < V
+ *   out[b * ld_o + i] = scale * (c_i - u_i) + u_i,   c = log_softmax(cond[b * ld_c + 0 .. V)),   u = log_softmax(uncond[b * ld_u + 0 .. V))
+ * in fp32, log_softmax evaluated as (z - max) - log(sum of exp(z - max)) and every difference, the product and the final sum rounded on their own (no fused
+ * multiply-add), IEEE throughout: -inf - -inf is NaN, as in the reference; a row with no entry above -inf, or with a +inf, is NaN everywhere.  A NaN logit
+ * counts as -inf before the formula (the convention of afk_decode_sample and afk_beam_step).  out may be cond (not uncond).  Any V >= 1, rows 4-byte aligned
+ * (16-byte loads and stores where a row's address allows them, the same values in the same threads where not); columns >= V are never read or written.
+ * Two plain launches on grid (ceil(V / 2048), B): the first writes {max, sum of exp} per 2 048-column chunk of both rows into ws, the second folds those pairs
+ * in one fixed order (by the whole block) and writes its chunk.  ws: afk_decode_cfg_workspace_floats(B, V) floats, no initialisation needed, not shared with a launch in flight on
+ * another stream.  Enqueue-only, no allocation, capturable, no counters and no atomics: the bits depend on the inputs and the shape alone.
+ * Refused: null pointers, B < 1 or > 65535, V < 1, a leading dimension below V, a workspace that is too small. */
+int64_t afk_decode_cfg_workspace_floats(int B, int V);
+int afk_decode_cfg(const float* cond, int64_t ld_c, const float* uncond, int64_t ld_u, float scale, float* out, int64_t ld_o, int B, int V, float* ws,
+                   int64_t ws_floats, void* stream);
 /* Logits processors on the device (csrc/decode_process.hip), one launch for B rows of fp32 logits [B][V] (row stride ld_logits >= V; any V >= 1, any B >= 1),
  * processed IN PLACE: the processors GenerationMixin._get_logits_processor (transformers/generation/utils.py:1174-1290) puts in front of the warpers, in its order -
  * RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor, MinNewTokensLengthLogitsProcessor, SuppressTokensLogitsProcessor,
