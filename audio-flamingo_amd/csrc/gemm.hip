@@ -260,10 +260,11 @@ hipEvent_t prof_next_event() {
 extern "C" int afk_gemm_set_variant(int v) {
     // v = base + 256*gm : base 0 auto, 1 = 128x128 kernel, 2 = 256x256 ping-pong kernel; bit 4 (16) = 8-byte epilogue stores (A/B knob, same results);
     // gm bits 0..5 = rasterization group height.  Everything else selects a timing probe or a rejected schedule and exists in
-    // -DAFK_PROBES builds only (gm bit 6: no epilogue = WRONG results, bit 7: raw dispatch order; base 3..13: gemm256w4 / f8 / p.hip).
+    // -DAFK_PROBES builds only (gm bit 6: no epilogue = WRONG results, bit 7: raw dispatch order; base 3..14: gemm256w4 / f8 / p / q.hip;
+    // base 15: the 256x256 ping-pong kernels - NT, NN and TN - on their previous K loop, same results: the A/B of profiles/gemm_tail.md).
     const int gm = (v >> 8) & 255, base = v & 15;
 #ifdef AFK_PROBES
-    AFK_REQUIRE(base >= 0 && base <= 14, "afk_gemm_set_variant: 14 = persistent tile loop with the next tile's prologue issued ahead of the epilogue stores (round-4 probe), 13 = 256x256 ping-pong as a persistent tile loop, 0 auto, 1 = 128x128, 2 = 256x256 8-wave ping-pong, 3 = 256x256 4-wave (4, 5: its timing probes), 6 = 256x256 8-wave free-running BK=64 (7, 8, 9: probes), 10 = 8-wave free-running BK=32 ring-10 (11: probe)");
+    AFK_REQUIRE(base >= 0 && base <= 15, "afk_gemm_set_variant: 15 = 256x256 8-wave ping-pong on its previous K loop (clamped tail prefetches), 14 = persistent tile loop with the next tile's prologue issued ahead of the epilogue stores (round-4 probe), 13 = 256x256 ping-pong as a persistent tile loop, 0 auto, 1 = 128x128, 2 = 256x256 8-wave ping-pong, 3 = 256x256 4-wave (4, 5: its timing probes), 6 = 256x256 8-wave free-running BK=64 (7, 8, 9: probes), 10 = 8-wave free-running BK=32 ring-10 (11: probe)");
 #else
     AFK_REQUIRE(base >= 0 && base <= 2, "afk_gemm_set_variant: variant %d is a probe / rejected schedule; this libafk.so was built without -DAFK_PROBES (make PROBES=1)", base);
     AFK_REQUIRE((gm & 0xc0) == 0, "afk_gemm_set_variant: gm bits 6 / 7 are timing probes (wrong results); this libafk.so was built without -DAFK_PROBES");
@@ -363,7 +364,7 @@ static int gemm_impl(int trans_a, int trans_b, const void* A, int64_t lda, const
     p.flags = flags;
     p.res_mod = res_mod;
     p.alpha = alpha;
-    p.gm = g_gm;
+    p.gm = g_gm | (g_variant == 15 ? 0x100 : 0);   // bit 8: previous K loop, reachable in -DAFK_PROBES builds only (afk_gemm_set_variant)
     p.splits = splits;
     p.ws = (float*)workspace;
     p.rope_cos = rope ? (const bf16*)rope->cos_t : nullptr;
@@ -396,7 +397,7 @@ static int gemm_impl(int trans_a, int trans_b, const void* A, int64_t lda, const
         return (e && e[0] == 'p' && e[1] == 'e') ? 13 : (e && e[0] == 'p') ? 2 : (e && e[0] == 'w') ? 3 : (e && e[0] == 'f') ? 10 : 0;  // pp | persist | w4 | f8
     }();
     // the fused SwiGLU forward exists in the ping-pong kernel only: it never takes a probe schedule
-    const int impl256 = (flags & (AFK_GEMM_SWIGLU_FWD | AFK_GEMM_ROPE)) ? 2 : g_variant >= 2 ? g_variant : (env_impl ? env_impl : g_256_impl);   // 2 pp | 3..9 w4 family | 10, 11 f8
+    const int impl256 = (flags & (AFK_GEMM_SWIGLU_FWD | AFK_GEMM_ROPE)) ? 2 : g_variant >= 2 ? (g_variant == 15 ? 2 : g_variant) : (env_impl ? env_impl : g_256_impl);   // 2 pp | 3..9 w4 family | 10, 11 f8
     const bool w4 = use256 && !trans_b && impl256 >= 3 && impl256 <= 9;
     const bool f8 = use256 && !trans_b && impl256 >= 10 && impl256 <= 12;
     const bool persist = use256 && !trans_b && impl256 == 13;

@@ -26,6 +26,8 @@
 // and counted waits before the barriers (vmcnt 6 / 8 / 2 / 8 after MEM_a / MFMA_a / MEM_b / MFMA_b) retire exactly the
 // class the NEXT segment of the other group reads (derivation in DESIGN.md §3); never vmcnt(0) in the steady state.  ds_reads are retired
 // (lgkmcnt(0)) before the barrier that ends a MEM segment, so a slot is never restaged under an outstanding read.
+// The last two K-tiles are peeled out of the loop (k_tile below): nothing is staged for tiles >= T, and the last wait of the kernel is the one that
+// retires Y(T-1) after MEM_a(T-1) - a wave reaches its epilogue with no LDS-DMA in flight.
 #include "gemm_common.h"
 
 namespace {
@@ -48,7 +50,8 @@ constexpr int LDS_BYTES = 2 * BUF_BYTES;  // 128 KiB
 // EPI: compile-time epilogue flags (gemm_common.h), -1 = runtime flags / narrow stores / split-K partials
 // MF: MFMA shape (gemm_common.h): 32 = 16 x v_mfma_f32_32x32x16_bf16 per MFMA segment, 16 = 32 x v_mfma_f32_16x16x32_bf16 (same cycles, same
 // fragments per segment, same 64 + 128 VGPRs); on N(0,1) operands the chip holds a higher clock on the second (profiles/gemm_mfma_shape_ab.md)
-template <int EPI, int MF>
+// OLDLOOP: make PROBES=1 builds only (afk_gemm_set_variant(15)) - the previous K loop, kept for the A/B of profiles/gemm_tail.md
+template <int EPI, int MF, bool OLDLOOP = false>
 __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -57,9 +60,12 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
     const int wm = wave >> 2, wn = wave & 3;  // wm doubles as the ping-pong group
     const int hi = lane >> 5, l31 = lane & 31;
 
+    // ---- prologue order: the first barrier waits for X0 alone, so the tile index and the six X sources come first and X0 leaves before anything else
+    // is computed; Y0 and X1 follow as soon as the Y sources exist; fragment offsets and accumulator zeroing run under the loads in flight
     int tm, tn;
     gemm_tile_of_block(p, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
+    const int T = p.K / BK;
 
     // ---- LDS-DMA sources.  unit u of an operand image = rows [8u, 8u+8).  X: 6 units per wave, Y: 2 units per wave.
     // X list (48): i<32 -> B unit i ; i>=32 -> A unit (i-32 < 8 ? i-32 : i-32+8)   (A rows 0..63, 128..191)
@@ -68,36 +74,24 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
     int xdst[6];
     const bf16* ysrc[2];
     int ydst[2];
-    {
-        const int lrow = lane >> 3, pos = lane & 7;
+    const int lrow = lane >> 3, pos = lane & 7;
 #pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const int i = wave + 8 * j;
-            const bool isB = i < 32;
-            const int unit = isB ? i : ((i - 32) < 8 ? (i - 32) : (i - 32) + 8);
-            const int rl = unit * 8 + lrow;
-            const int chunk = pos ^ ((rl >> 1) & 7);
-            if (isB) {
-                // SWIGLU_FWD: N-tile tn = 128 gate rows [128 tn, +128) followed by the 128 up rows [I + 128 tn, +128) of the fused weight,
-                // so that one workgroup holds gate AND up of the same 128 intermediate features
-                const int r = (EPI == AFK_GEMM_SWIGLU_FWD) ? (rl < 128 ? tn * 128 + rl : (p.N >> 1) + tn * 128 + rl - 128) : min(n0 + rl, p.N - 1);
-                xsrc[j] = p.B + (int64_t)r * p.ldb + chunk * 8;
-            } else {
-                const int r = min(m0 + rl, p.M - 1);
-                xsrc[j] = p.A + (int64_t)r * p.lda + chunk * 8;
-            }
-            xdst[j] = (isB ? OP_BYTES : 0) + unit * 1024;
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int jj = wave + 8 * j;
-            const int unit = jj < 8 ? 8 + jj : 16 + jj;
-            const int rl = unit * 8 + lrow;
-            const int chunk = pos ^ ((rl >> 1) & 7);
+    for (int j = 0; j < 6; ++j) {
+        const int i = wave + 8 * j;
+        const bool isB = i < 32;
+        const int unit = isB ? i : ((i - 32) < 8 ? (i - 32) : (i - 32) + 8);
+        const int rl = unit * 8 + lrow;
+        const int chunk = pos ^ ((rl >> 1) & 7);
+        if (isB) {
+            // SWIGLU_FWD: N-tile tn = 128 gate rows [128 tn, +128) followed by the 128 up rows [I + 128 tn, +128) of the fused weight,
+            // so that one workgroup holds gate AND up of the same 128 intermediate features
+            const int r = (EPI == AFK_GEMM_SWIGLU_FWD) ? (rl < 128 ? tn * 128 + rl : (p.N >> 1) + tn * 128 + rl - 128) : min(n0 + rl, p.N - 1);
+            xsrc[j] = p.B + (int64_t)r * p.ldb + chunk * 8;
+        } else {
             const int r = min(m0 + rl, p.M - 1);
-            ysrc[j] = p.A + (int64_t)r * p.lda + chunk * 8;
-            ydst[j] = unit * 1024;
+            xsrc[j] = p.A + (int64_t)r * p.lda + chunk * 8;
         }
+        xdst[j] = (isB ? OP_BYTES : 0) + unit * 1024;
     }
     auto issue_x = [&](int t) {
         char* base = smem + (t & 1) * BUF_BYTES;
@@ -113,6 +107,22 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
         for (int j = 0; j < 2; ++j)
             __builtin_amdgcn_global_load_lds((gbl_void*)(ysrc[j] + koff), (lds_void*)(base + ydst[j]), 16, 0, 0);
     };
+    __builtin_amdgcn_sched_barrier(0);
+    issue_x(0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int jj = wave + 8 * j;
+        const int unit = jj < 8 ? 8 + jj : 16 + jj;
+        const int rl = unit * 8 + lrow;
+        const int chunk = pos ^ ((rl >> 1) & 7);
+        const int r = min(m0 + rl, p.M - 1);
+        ysrc[j] = p.A + (int64_t)r * p.lda + chunk * 8;
+        ydst[j] = unit * 1024;
+    }
+    issue_y(0);
+    if (T > 1) issue_x(1);   // a one-tile reduction (T = 1) stages nothing beyond its own tile
+    __builtin_amdgcn_sched_barrier(0);
 
     // ---- fragment offsets (bytes within an operand image); the swizzle term is lane-constant
     // fragment x = 0..3 of a 32-row tile (gemm_common.h: MF = 32: k-step x; MF = 16: 16-row half x >> 1, k-step x & 1)
@@ -124,17 +134,17 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
 
     GemmAcc<MF> acc;
     acc.zero();
+    // all of the above runs here, under the loads in flight, not behind the barrier (afk_pin)
+#pragma unroll
+    for (int x = 0; x < 4; ++x) afk_pin(koffb[x]);
+    int a_row0_ = a_row0, b_row0_ = b_row0;
+    afk_pin(a_row0_);
+    afk_pin(b_row0_);
+    acc.pin();
 
-    const int T = p.K / BK;
-    // ---- prologue: X0 Y0 X1, then make X0 visible to everyone
-    issue_x(0);
-    issue_y(0);
-    if (T > 1) {
-        issue_x(1);
-        AFK_VMCNT(8);
-    } else {
-        AFK_VMCNT(2);
-    }
+    // ---- make X0 visible to everyone: at most Y0 (2) + X1 (6) stay in flight
+    if (T > 1) AFK_VMCNT(8);
+    else AFK_VMCNT(2);
     AFK_BARRIER();
     if (wm == 1) AFK_BARRIER();  // group 1 runs one segment behind group 0
 
@@ -172,11 +182,26 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
     };
     using afk_c2 = std::integral_constant<int, 2>;
 #define AFK_MFMA4(ACC0, g) mfma_group(std::integral_constant<int, ACC0>{}, std::integral_constant<int, g>{})
-    // Branch-free steady state: past the last K-tile the prefetch index is clamped to T-1, i.e. the tail re-loads the
-    // last tile into slots nobody reads again (dead by the same lifetime argument), so the vmcnt ladder never changes.
-    for (int t = 0; t < T; ++t) {
+    // One K-tile.  MODE 0 = steady state (tiles 0 .. T-3): stages Y(t+1) in MFMA_a and X(t+2) in MFMA_b, ladder 6 / 8 / 2 / 8 (header).
+    // The last two tiles are peeled out of the loop: they stage nothing past tile T-1, and their waits follow from what is still in flight -
+    //   MODE 1 = tile T-2: enters with Y(T-2) [2], X(T-1) [6] outstanding, in this order.
+    //       after MEM_a : the other group's MEM_b(T-2) reads Y(T-2) next  -> only X(T-1) may stay out          -> vmcnt(6)   (as in the steady state)
+    //       MFMA_a      : issues Y(T-1); outstanding X(T-1) [6] Y(T-1) [2] = 8: the steady vmcnt(8) asks for nothing -> no wait
+    //       after MEM_b : the other group's MEM_a(T-1) reads X(T-1) next  -> only Y(T-1) may stay out          -> vmcnt(2)   (as in the steady state)
+    //       MFMA_b      : X(T) does not exist: no DMA; outstanding Y(T-1) [2], nobody reads it before MEM_b(T-1)  -> no wait
+    //   MODE 2 = tile T-1: enters with Y(T-1) [2] outstanding, issues nothing.
+    //       after MEM_a : the other group's MEM_b(T-1) reads Y(T-1) next  -> nothing may stay out               -> vmcnt(0)
+    //       MFMA_a, MEM_b, MFMA_b: nothing in flight -> no wait.  The wave reaches the epilogue with an empty vector-memory queue by construction, so
+    //       no drain precedes it, and the epilogues that reuse the operand buffers (SwiGLU forward, RoPE) see no LDS-DMA behind them.
+    //   T = 1: the prologue issued X0 Y0 only and left Y0 [2] out: exactly the entry state of MODE 2.  T = 2: the prologue left Y0 [2] X1 [6]: the
+    //   entry state of MODE 1 at t = 0.  The barriers are those of the steady state (4 per tile), so the two groups stay one segment apart.
+    //   MODE 3 (make PROBES=1 only, afk_gemm_set_variant(15)) = the previous loop: every tile a MODE 0 tile with the prefetch index clamped to T-1,
+    //   i.e. the last two tiles re-load tile T-1 into slots nobody reads, and a vmcnt(0) drains them in front of the epilogue.
+    auto k_tile = [&](int t, auto mode_) __attribute__((always_inline)) {
+        constexpr int MODE = decltype(mode_)::value;
+        constexpr bool STAGE_Y = MODE != 2, STAGE_X = MODE == 0 || MODE == 3;
         const char* buf = smem + (t & 1) * BUF_BYTES;
-        const int t1 = min(t + 1, T - 1), t2 = min(t + 2, T - 1);
+        const int t1 = MODE == 3 ? min(t + 1, T - 1) : t + 1, t2 = MODE == 3 ? min(t + 2, T - 1) : t + 2;
         const int e1 = (t + 1) & 1, e2 = t & 1;  // destination buffer parity follows the UNclamped tile index
         const int64_t oy = (int64_t)t1 * BK, ox = (int64_t)t2 * BK;
         char* by = smem + e1 * BUF_BYTES;
@@ -185,53 +210,67 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) bf[j][s] = *(const bf16x8*)(buf + b_row0 + j * 32 * ROWB + koffb[s]);
+            for (int s = 0; s < 4; ++s) bf[j][s] = *(const bf16x8*)(buf + b_row0_ + j * 32 * ROWB + koffb[s]);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) af[i][s] = *(const bf16x8*)(buf + a_row0 + i * 32 * ROWB + koffb[s]);
+            for (int s = 0; s < 4; ++s) af[i][s] = *(const bf16x8*)(buf + a_row0_ + i * 32 * ROWB + koffb[s]);
         AFK_LGKMCNT0();
-        AFK_VMCNT(6);
+        if constexpr (MODE == 2) AFK_VMCNT(0);
+        else AFK_VMCNT(6);
         AFK_BARRIER();
         // ================= MFMA_a(t) (+ Y(t+1): 2 pieces)
         __builtin_amdgcn_s_setprio(1);
         AFK_MFMA4(0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_global_load_lds((gbl_void*)(ysrc[0] + oy), (lds_void*)(by + ydst[0]), 16, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (STAGE_Y) {
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_global_load_lds((gbl_void*)(ysrc[0] + oy), (lds_void*)(by + ydst[0]), 16, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         AFK_MFMA4(0, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_global_load_lds((gbl_void*)(ysrc[1] + oy), (lds_void*)(by + ydst[1]), 16, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (STAGE_Y) {
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_global_load_lds((gbl_void*)(ysrc[1] + oy), (lds_void*)(by + ydst[1]), 16, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         AFK_MFMA4(0, 2);
         AFK_MFMA4(0, 3);
         __builtin_amdgcn_s_setprio(0);
-        AFK_VMCNT(8);
+        if constexpr (STAGE_X) AFK_VMCNT(8);
         AFK_BARRIER();
         // ================= MEM_b(t): A rows 64..127
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) af[i][s] = *(const bf16x8*)(buf + a_row0 + (i + 2) * 32 * ROWB + koffb[s]);
+            for (int s = 0; s < 4; ++s) af[i][s] = *(const bf16x8*)(buf + a_row0_ + (i + 2) * 32 * ROWB + koffb[s]);
         AFK_LGKMCNT0();
-        AFK_VMCNT(2);
+        if constexpr (STAGE_Y) AFK_VMCNT(2);
         AFK_BARRIER();
         // ================= MFMA_b(t) (+ X(t+2): 6 pieces)
         __builtin_amdgcn_s_setprio(1);
         afk_static_for<8>([&](auto q_) {
             constexpr int piece = decltype(q_)::value;  // 0..7, pieces 0..5 carry a DMA
             mfma_slot(afk_c2{}, q_);
-            if constexpr (piece < 6) {
+            if constexpr (STAGE_X && piece < 6) {
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_global_load_lds((gbl_void*)(xsrc[piece] + ox), (lds_void*)(bx + xdst[piece]), 16, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
         __builtin_amdgcn_s_setprio(0);
-        AFK_VMCNT(8);
+        if constexpr (STAGE_X) AFK_VMCNT(8);
         AFK_BARRIER();
+    };
+    if constexpr (OLDLOOP) {   // the previous K loop (T = 1 has no prefetch to clamp: it runs as the last tile of the new one)
+        const int told = T > 1 ? T : 0;
+        for (int t = 0; t < told; ++t) k_tile(t, std::integral_constant<int, 3>{});
+        if (T == 1) k_tile(0, std::integral_constant<int, 2>{});
+        AFK_VMCNT(0);
+    } else {
+        for (int t = 0; t < T - 2; ++t) k_tile(t, std::integral_constant<int, 0>{});   // branch-free steady state
+        if (T > 1) k_tile(T - 2, std::integral_constant<int, 1>{});
+        k_tile(T - 1, std::integral_constant<int, 2>{});
     }
-    AFK_VMCNT(0);  // no LDS-DMA may be in flight when the workgroup releases its LDS
 #undef AFK_MFMA4
     if (wm == 0) AFK_BARRIER();  // equalise barrier counts
 
@@ -380,12 +419,12 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_k256(GemmArgs p) {
 #define AFK_EPI_LIST(X) X(0) X(AFK_GEMM_BIAS) X(AFK_GEMM_RESIDUAL) X(AFK_GEMM_BIAS | AFK_GEMM_RESIDUAL) X(AFK_GEMM_BIAS | AFK_GEMM_GELU) \
     X(AFK_GEMM_BIAS | AFK_GEMM_GELU | AFK_GEMM_RESIDUAL) X(AFK_GEMM_ACCUM) X(AFK_GEMM_SWIGLU_FWD) X(AFK_GEMM_SWIGLU_BWD) X(AFK_GEMM_ROPE) X(AFK_GEMM_ROPE | AFK_GEMM_BIAS) X(-1)
 
-template <int MF>
+template <int MF, bool OLD = false>
 static int launch_gemm256(const GemmArgs& p, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
 #define AFK_SET(F)                                                                                                                           \
-    if (hipFuncSetAttribute((const void*)gemm_nt_bf16_k256<(F), MF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) \
+    if (hipFuncSetAttribute((const void*)gemm_nt_bf16_k256<(F), MF, OLD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) \
         return afk_set_error(AFK_ERR_LAUNCH, "gemm256: cannot reserve %d bytes of LDS", LDS_BYTES);
         AFK_EPI_LIST(AFK_SET)
 #undef AFK_SET
@@ -397,18 +436,21 @@ static int launch_gemm256(const GemmArgs& p, hipStream_t st) {
 #define AFK_CASE(F)                                                                                              \
     case (F):                                                                                                    \
         if ((F) == -1) afk_count(AFK_CNT_GEMM_GENERIC);                                                          \
-        hipLaunchKernelGGL((gemm_nt_bf16_k256<(F), MF>), dim3((unsigned)nwg), dim3(512), LDS_BYTES, st, p);      \
+        hipLaunchKernelGGL((gemm_nt_bf16_k256<(F), MF, OLD>), dim3((unsigned)nwg), dim3(512), LDS_BYTES, st, p);      \
         break;
         AFK_EPI_LIST(AFK_CASE)
 #undef AFK_CASE
         default:   // an epilogue outside the list: runtime-flag instantiation
             afk_count(AFK_CNT_GEMM_GENERIC);
-            hipLaunchKernelGGL((gemm_nt_bf16_k256<-1, MF>), dim3((unsigned)nwg), dim3(512), LDS_BYTES, st, p);
+            hipLaunchKernelGGL((gemm_nt_bf16_k256<-1, MF, OLD>), dim3((unsigned)nwg), dim3(512), LDS_BYTES, st, p);
     }
     return AFK_OK;
 }
 
 int afk_launch_gemm256(const GemmArgs& p, int mf, hipStream_t st) {
+#ifdef AFK_PROBES
+    if (AFK_GM_OLDLOOP(p)) return mf == 16 ? launch_gemm256<16, true>(p, st) : launch_gemm256<32, true>(p, st);
+#endif
     if constexpr ((AFK_MFMA_SHAPES_NT & 2) != 0)
         if (mf == 16) return launch_gemm256<16>(p, st);
     if constexpr ((AFK_MFMA_SHAPES_NT & 1) != 0)

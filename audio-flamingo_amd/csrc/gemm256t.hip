@@ -89,7 +89,8 @@ __device__ __forceinline__ TSrc tsrc(const bf16* mat, int unit, int col0, int nc
 
 // EPI: compile-time epilogue flags (gemm_common.h: one small epilogue instead of every variant inlined at each store site), -1 = runtime
 // MF: MFMA shape, 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16 (gemm_common.h; only fragments, MFMA calls and accumulator indexing differ)
-template <bool AT, int EPI, int MF>
+// OLDLOOP: make PROBES=1 builds only (afk_gemm_set_variant(15)) - the previous K loop, kept for the A/B of profiles/gemm_tail.md
+template <bool AT, int EPI, int MF, bool OLDLOOP = false>
 __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -123,8 +124,8 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
     TSrc tr_src[NX + NY];         // reduction-major sources (advance by t*64 rows)
     int64_t tr_ld[NX + NY];
     int dst[NX + NY];
-#pragma unroll
-    for (int j = 0; j < NX + NY; ++j) {
+    const bf16* tbase[NX + NY];
+    auto make_piece = [&](int j) __attribute__((always_inline)) {
         const bool isx = j < NX;
         const int jj = isx ? j : j - NX;
         an_src[j] = nullptr;
@@ -153,16 +154,17 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
             an_src[j] = Abase + (int64_t)r * p.lda + chunk * 8;
             dst[j] = unit * 1024;
         }
-    }
+        tbase[j] = (AT || j < 4) ? tr_src[j].base + (int64_t)tr_src[j].krow * tr_ld[j] : nullptr;
+    };
     // reduction-major pieces: per-lane base already at the piece's k-row, advanced per K-tile by a wave-uniform (scalar) offset - one 64-bit
     // add per DMA.  The row clamp (k-rows beyond the reduction length) only exists in a ragged LAST tile: that one takes the general form.
     // (The general form on every piece - per-lane min + 64-bit multiply, ~10 VALU between two MFMAs, eight times per K-tile - cost the TN
     // kernel ~8 % against the NT kernel: profiles/r02_gemm_probes.md §12.)
-    const bf16* tbase[NX + NY];
+    // Prologue order: the first barrier waits for X0 alone, so only the X pieces are set up ahead of the first LDS-DMA; the Y pieces follow X0, then Y0
+    // and X1 leave, and the read offsets and the accumulator zeroing run under the loads in flight.
 #pragma unroll
-    for (int j = 0; j < NX + NY; ++j) tbase[j] = (AT || j < 4) ? tr_src[j].base + (int64_t)tr_src[j].krow * tr_ld[j] : nullptr;
+    for (int j = 0; j < NX; ++j) make_piece(j);
     GemmAcc<MF> acc;
-    acc.zero();
 
     const bool ragged = (KL % BK) != 0;
   // the whole pipeline twice: RAG = false (K a multiple of 64: every training shape) never clamps, RAG = true is the general form
@@ -181,6 +183,19 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
         return an_src[j] + (int64_t)t * BK;
     };
     auto issue = [&](int j, int t_src, int parity) { AFK_DMA_PTR(src_of(j, t_src), smem + parity * BUF_BYTES + dst[j]); };
+
+    // ------------------------------------------------------------------ prologue: X0 | Y0 X1 (a one-tile reduction, T = 1, stages no X1)
+#pragma unroll
+    for (int j = 0; j < NX; ++j) issue(j, 0, 0);
+#pragma unroll
+    for (int j = 0; j < NY; ++j) make_piece(NX + j);
+#pragma unroll
+    for (int j = 0; j < NY; ++j) issue(NX + j, 0, 0);
+    if (T > 1) {
+#pragma unroll
+        for (int j = 0; j < NX; ++j) issue(j, 1, 1);
+    }
+    acc.zero();
 
     // lane-constant tr-read offsets: B tiles wn*2+j, A tiles wm*4+i (TN); MF = 16: [tile][h][pc] = 16-column half h of the 32-column tile
     constexpr int NH = MF == 16 ? 2 : 1;
@@ -209,28 +224,52 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
     int koffb[4];
 #pragma unroll
     for (int x = 0; x < 4; ++x) koffb[x] = gemm_frag_rowoff<MF>(x) * 128 + gemm_frag_koff<MF>(x, lane);
-    const int a_row0 = (wm * 128 + gemm_frag_row<MF>(lane)) * 128;
-
-    // ------------------------------------------------------------------ prologue: X0 Y0 X1
+    int a_row0 = (wm * 128 + gemm_frag_row<MF>(lane)) * 128;
+    // all of the above runs here, under the loads in flight, not behind the barrier (afk_pin)
 #pragma unroll
-    for (int j = 0; j < NX; ++j) issue(j, 0, 0);
+    for (int j = 0; j < 2; ++j)
 #pragma unroll
-    for (int j = 0; j < NY; ++j) issue(NX + j, 0, 0);
-    {
-        const int t1 = min(1, T - 1);
+        for (int h = 0; h < NH; ++h)
 #pragma unroll
-        for (int j = 0; j < NX; ++j) issue(j, t1, 1);
+            for (int pc = 0; pc < 2; ++pc) afk_pin(tob[j][h][pc]);
+    if constexpr (AT) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+#pragma unroll
+                for (int pc = 0; pc < 2; ++pc) afk_pin(toa[i][h][pc]);
+    } else {
+#pragma unroll
+        for (int x = 0; x < 4; ++x) afk_pin(koffb[x]);
+        afk_pin(a_row0);
     }
-    if (AT) AFK_VMCNT(8); else AFK_VMCNT(8);  // NY + NX outstanding allowed: X0 has landed
+    acc.pin();
+
+    // X0 visible to everyone: at most Y0 (NY) + X1 (NX) stay in flight
+    if (T > 1) AFK_VMCNT(8);
+    else if (AT) AFK_VMCNT(4);
+    else AFK_VMCNT(2);
     AFK_BARRIER();
     if (wm == 1) AFK_BARRIER();
 
     bf16x8 bf[2][4], af[AT ? 4 : 2][AT ? 2 : 4];
     const uint32_t lds0 = afk_lds_addr(smem);
-    for (int t = 0; t < T; ++t) {
+    // One K-tile, as k_tile of gemm256.hip (the derivation is there; NX / NY = 6 / 2 for NN, 4 / 4 for TN, issue order X0 Y0 X1 | Y1 X2 | ...):
+    //   MODE 0 = steady state, tiles 0 .. T-3: Y(t+1) staged in the first MFMA segment, X(t+2) in the second; waits NX / 8 / NY / 8
+    //   MODE 1 = tile T-2: enters with Y(T-2) [NY] X(T-1) [NX] out.  After the first MEM segment Y(T-2) must be in -> vmcnt(NX); the first MFMA segment
+    //            issues Y(T-1): 8 out, no wait; after the second MEM segment X(T-1) must be in -> vmcnt(NY); the second MFMA segment stages nothing
+    //            (X(T) does not exist) and waits for nothing
+    //   MODE 2 = tile T-1: enters with Y(T-1) [NY] out and stages nothing.  After the first MEM segment -> vmcnt(0); no wait after that: the epilogue
+    //            starts with nothing in flight.  T = 1 enters here from the prologue (Y0 out), T = 2 enters MODE 1 (Y0 X1 out).
+    //   MODE 3 (make PROBES=1 only, afk_gemm_set_variant(15)) = the previous loop: MODE 0 with the prefetch index clamped to T-1, drained by a vmcnt(0)
+    // The ragged last tile of TN (kvalid < 64) is tile T-1 in every mode: its zeroing of the A fragments and the clamped source rows (src_of) are untouched.
+    auto k_tile = [&](int t, auto mode_) __attribute__((always_inline)) {
+        constexpr int MODE = decltype(mode_)::value;
+        constexpr bool STAGE_Y = MODE != 2, STAGE_X = MODE == 0 || MODE == 3;
         const char* buf = smem + (t & 1) * BUF_BYTES;
         const uint32_t lbuf = lds0 + (t & 1) * BUF_BYTES;
-        const int t1 = min(t + 1, T - 1), t2 = min(t + 2, T - 1);
+        const int t1 = MODE == 3 ? min(t + 1, T - 1) : t + 1, t2 = MODE == 3 ? min(t + 2, T - 1) : t + 2;
         const int e1 = (t + 1) & 1, e2 = t & 1;
         if constexpr (!AT) {
             // ================= NN  MEM_a: Bt fragments (whole tile) + A rows 0..63
@@ -242,7 +281,8 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
 #pragma unroll
                 for (int s = 0; s < 4; ++s) af[i][s] = *(const bf16x8*)(buf + a_row0 + i * 32 * 128 + koffb[s]);
             AFK_LGKMCNT0();
-            AFK_VMCNT(6);
+            if constexpr (MODE == 2) AFK_VMCNT(0);
+            else AFK_VMCNT(6);
             AFK_BARRIER();
             // ================= MFMA_a (+ Y(t+1))
             __builtin_amdgcn_s_setprio(1);
@@ -260,10 +300,10 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
 #pragma unroll
                         for (int jt = 0; jt < 4; ++jt) acc.mma(2 * i + ih, jt, bf[jt >> 1][2 * (jt & 1) + s], af[i][2 * ih + s]);
                 }
-                if constexpr (g < 2) issue(NX + g, t1, e1);
+                if constexpr (STAGE_Y && g < 2) issue(NX + g, t1, e1);
             });
             __builtin_amdgcn_s_setprio(0);
-            AFK_VMCNT(8);
+            if constexpr (STAGE_X) AFK_VMCNT(8);
             AFK_BARRIER();
             // ================= MEM_b: A rows 64..127
 #pragma unroll
@@ -271,7 +311,7 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
 #pragma unroll
                 for (int s = 0; s < 4; ++s) af[i][s] = *(const bf16x8*)(buf + a_row0 + (i + 2) * 32 * 128 + koffb[s]);
             AFK_LGKMCNT0();
-            AFK_VMCNT(2);
+            if constexpr (STAGE_Y) AFK_VMCNT(2);
             AFK_BARRIER();
             // ================= MFMA_b (+ X(t+2))
             __builtin_amdgcn_s_setprio(1);
@@ -286,10 +326,10 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
 #pragma unroll
                     for (int jt = 0; jt < 4; ++jt) acc.mma(2 * (2 + i) + ih, jt, bf[jt >> 1][2 * (jt & 1) + s], af[i][2 * ih + s]);
                 }
-                if constexpr (piece < 6) issue(piece, t2, e2);
+                if constexpr (STAGE_X && piece < 6) issue(piece, t2, e2);
             });
             __builtin_amdgcn_s_setprio(0);
-            AFK_VMCNT(8);
+            if constexpr (STAGE_X) AFK_VMCNT(8);
             AFK_BARRIER();
         } else {
             const int kvalid = KL - t * BK;  // < 64 only on a ragged last tile
@@ -324,7 +364,12 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
                                 if (dead) af[i][s][e] = (bf16)0.f;
                         }
                 }
-                AFK_VMCNT(4);
+                // after MEM of phase 0: Y(t) must be in (X(t+1) may stay out); of phase 1: X(t+1) must be in (Y(t+1) may stay out)
+                if constexpr (MODE == 2) {
+                    if (ph == 0) AFK_VMCNT(0);
+                } else {
+                    AFK_VMCNT(4);
+                }
                 AFK_BARRIER();
                 // ================= MFMA (+ Y(t+1) in phase 0, X(t+2) in phase 1: 4 pieces each)
                 __builtin_amdgcn_s_setprio(1);
@@ -340,17 +385,29 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
                         for (int jt = 0; jt < 4; ++jt) acc.mma(2 * i + ih, jt, bf[jt >> 1][jt & 1], af[i][ih]);
                     }
                     if constexpr ((piece & 1) == 0) {
-                        if (ph == 0) issue(NX + (piece >> 1), t1, e1);
-                        else issue(piece >> 1, t2, e2);
+                        if (ph == 0) {
+                            if constexpr (STAGE_Y) issue(NX + (piece >> 1), t1, e1);
+                        } else {
+                            if constexpr (STAGE_X) issue(piece >> 1, t2, e2);
+                        }
                     }
                 });
                 __builtin_amdgcn_s_setprio(0);
-                AFK_VMCNT(8);
+                if constexpr (STAGE_X) AFK_VMCNT(8);
                 AFK_BARRIER();
             }
         }
+    };
+    if constexpr (OLDLOOP) {   // the previous K loop (T = 1 has no prefetch to clamp: it runs as the last tile of the new one)
+        const int told = T > 1 ? T : 0;
+        for (int t = 0; t < told; ++t) k_tile(t, std::integral_constant<int, 3>{});
+        if (T == 1) k_tile(0, std::integral_constant<int, 2>{});
+        AFK_VMCNT(0);
+    } else {
+        for (int t = 0; t < T - 2; ++t) k_tile(t, std::integral_constant<int, 0>{});   // branch-free steady state
+        if (T > 1) k_tile(T - 2, std::integral_constant<int, 1>{});
+        k_tile(T - 1, std::integral_constant<int, 2>{});
     }
-    AFK_VMCNT(0);
     if (wm == 0) AFK_BARRIER();
   };
     if (ragged) pipeline(std::true_type{});
@@ -367,12 +424,12 @@ __global__ __launch_bounds__(512, 1) void gemm_xt_bf16_k256(GemmArgs p) {
 // weight gradients write or accumulate plain bf16 (flags 0 / ACCUM); the generic instantiation serves split-K partials and the rest
 #define AFK_EPI_LIST(X) X(0) X(AFK_GEMM_ACCUM) X(-2) X(-1)
 
-template <bool AT, int MF>
+template <bool AT, int MF, bool OLD = false>
 static int launch_gemm256t(const GemmArgs& p, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
 #define AFK_SET(F)                                                                                                                              \
-    if (hipFuncSetAttribute((const void*)gemm_xt_bf16_k256<AT, (F), MF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) \
+    if (hipFuncSetAttribute((const void*)gemm_xt_bf16_k256<AT, (F), MF, OLD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) \
         return afk_set_error(AFK_ERR_LAUNCH, "gemm256t: cannot reserve %d bytes of LDS", LDS_BYTES);
         AFK_EPI_LIST(AFK_SET)
 #undef AFK_SET
@@ -386,18 +443,23 @@ static int launch_gemm256t(const GemmArgs& p, hipStream_t st) {
 #define AFK_CASE(F)                                                                                        \
     case (F):                                                                                              \
         if ((F) == -1) afk_count(AFK_CNT_GEMM_GENERIC);                                                    \
-        hipLaunchKernelGGL((gemm_xt_bf16_k256<AT, (F), MF>), grid, dim3(512), LDS_BYTES, st, p);           \
+        hipLaunchKernelGGL((gemm_xt_bf16_k256<AT, (F), MF, OLD>), grid, dim3(512), LDS_BYTES, st, p);           \
         break;
         AFK_EPI_LIST(AFK_CASE)
 #undef AFK_CASE
         default:   // an epilogue outside the list: runtime-flag instantiation
             afk_count(AFK_CNT_GEMM_GENERIC);
-            hipLaunchKernelGGL((gemm_xt_bf16_k256<AT, -1, MF>), grid, dim3(512), LDS_BYTES, st, p);
+            hipLaunchKernelGGL((gemm_xt_bf16_k256<AT, -1, MF, OLD>), grid, dim3(512), LDS_BYTES, st, p);
     }
     return AFK_OK;
 }
 
 int afk_launch_gemm256t(const GemmArgs& p, int trans_a, int mf, hipStream_t st) {
+#ifdef AFK_PROBES
+    if (AFK_GM_OLDLOOP(p))
+        return trans_a ? (mf == 16 ? launch_gemm256t<true, 16, true>(p, st) : launch_gemm256t<true, 32, true>(p, st))
+                       : (mf == 16 ? launch_gemm256t<false, 16, true>(p, st) : launch_gemm256t<false, 32, true>(p, st));
+#endif
     if (trans_a) {
         if constexpr ((AFK_MFMA_SHAPES_TN & 2) != 0)
             if (mf == 16) return launch_gemm256t<true, 16>(p, st);

@@ -29,12 +29,14 @@ struct GemmArgs {
     const bf16* rope_sin_lanes;
 };
 
-// Probe bits of GemmArgs::gm (bit 6 = kernel WITHOUT its epilogue: wrong results; bit 7 = raw dispatch order) and the three rejected 256x256
+// Probe bits of GemmArgs::gm (bit 6 = kernel WITHOUT its epilogue: wrong results; bit 7 = raw dispatch order; bit 8, read by the launchers only = the
+// OLDLOOP instantiation of the 256x256 kernels, i.e. their previous K loop: afk_gemm_set_variant(15), profiles/gemm_tail.md) and the three rejected 256x256
 // schedules (gemm256w4 / gemm256f8 / gemm256p.hip, profiles/r02_gemm_probes.md) exist only in -DAFK_PROBES builds (make PROBES=1).  The
 // default library compiles the branches away and afk_gemm_set_variant() rejects the values that select them.
 #ifdef AFK_PROBES
 #define AFK_GM_NOEPI(p) (((p).gm & 0x40) != 0)
 #define AFK_GM_RAW(p) (((p).gm & 0x80) != 0)
+#define AFK_GM_OLDLOOP(p) (((p).gm & 0x100) != 0)
 #else
 #define AFK_GM_NOEPI(p) false
 #define AFK_GM_RAW(p) false
@@ -167,6 +169,11 @@ __device__ __forceinline__ constexpr int gemm_frag_rowoff(int x) { return MF == 
 // block(i, j) hands one 32 x 32 block to the epilogue as 16 registers b[8 t + 4 h + e]:
 //   MF = 32: the accumulator itself (t = q >> 1, h = q & 1)
 //   MF = 16: tile (2 i + h, 2 j + t), so that the wide form below is the same code with v_permlane16_swap in place of v_permlane32_swap
+// Keeps the computation of a lane value where the source puts it: without a use in front of the first barrier the compiler sinks the prologue's set-up
+// (fragment offsets, accumulator zeroing) behind that barrier, out of the shadow of the first LDS-DMA loads and onto the critical path of the first tile.
+template <class T>
+__device__ __forceinline__ void afk_pin(T& v) { asm volatile("" : "+v"(v)); }
+
 template <int MF>
 struct GemmAcc;
 template <>
@@ -179,6 +186,12 @@ struct GemmAcc<32> {
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) v[i][j][e] = 0.f;
+    }
+    __device__ __forceinline__ void pin() {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) afk_pin(v[i][j]);
     }
     // acc[i][j] += A rows (32 i ..) x B rows (32 j ..) over the k of fragment pair (xa, xb): one MFMA, xa == xb == k-step
     __device__ __forceinline__ void mma(int i, int j, const bf16x8& b, const bf16x8& a) { v[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b, a, v[i][j], 0, 0, 0); }
@@ -194,6 +207,12 @@ struct GemmAcc<16> {
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[i][j][e] = 0.f;
+    }
+    __device__ __forceinline__ void pin() {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) afk_pin(v[i][j]);
     }
     __device__ __forceinline__ void mma(int it, int jt, const bf16x8& b, const bf16x8& a) { v[it][jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, v[it][jt], 0, 0, 0); }
     __device__ __forceinline__ f32x16 block(int i, int j) const {

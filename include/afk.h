@@ -68,7 +68,8 @@ int afk_prof_dump(const char* host_path);
  */
 /* kernel variant override for tests/benchmarks: 0 auto (by tile count), 1 = 128x128x64 kernel, 2 = 256x256x64 ping-pong kernel; + 16 = 8-byte epilogue
  * stores (same results); + 256 * g (g = 1..63) = rasterization group height.  Any other value selects a timing probe or a rejected schedule: those
- * exist only in -DAFK_PROBES builds (make PROBES=1) and are refused (AFK_ERR_ARG) by the default library. */
+ * exist only in -DAFK_PROBES builds (make PROBES=1) and are refused (AFK_ERR_ARG) by the default library.  Among them 15 = the 256x256 kernels (NT, NN,
+ * TN) on their previous K loop (clamped tail prefetches, same results): the A/B of profiles/gemm_tail.md. */
 int afk_gemm_set_variant(int variant);
 /* MFMA shape of the 256x256 kernels (NT, NN, TN): 0 = the dispatch rule (csrc/gemm.hip gemm_mfma_of), 1 = v_mfma_f32_32x32x16_bf16, 2 = v_mfma_f32_16x16x32_bf16.
  * The environment variable AFK_GEMM_MFMA (0 | 1 | 2, read once at the first 256x256 launch) sets the same thing for a whole process; a call with v != 0

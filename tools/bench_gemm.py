@@ -1,7 +1,9 @@
 """GEMM microbenchmark on the AF3-7B shapes (random data, guide rule 25): the two 256x256 NT kernels (v2 = 8-wave ping-pong, v3 = 4-wave
 128x128 per wave), HIP-event timed through afk_prof_*.   python tools/bench_gemm.py [zeros]   (zeros: zero-filled operands = DVFS probe)
     python tools/bench_gemm.py mfma [out.json]    the step's NT / NN / TN shapes on each MFMA shape the library carries (ops.gemm_set_mfma 1 = 32x32x16,
-    2 = 16x16x32), alternating shape by shape: 5 warm + 25 timed launches each, HIP events per launch -> median / min / max per row"""
+    2 = 16x16x32), alternating shape by shape: 5 warm + 25 timed launches each, HIP events per launch -> median / min / max per row
+    python tools/bench_gemm.py libs OTHER_LIBAFK_SO [out.json]   the same rows on two builds of the library in one process - the loaded one ("this") and
+    OTHER ("other", e.g. the parent commit's build) - alternating launch by launch; each on its own dispatch rule, 256x256 kernels forced"""
 import sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,15 +20,73 @@ SHAPES = [  # (name, M, N, K)
 dev = torch.device("cuda")
 
 
-def mfma_ab(out_path):
-    """per-shape A/B of the MFMA shapes (profiles/gemm_mfma_shape_ab.md table (c))"""
-    import statistics
+def step_rows():
+    """the step's NT / NN / TN shapes (table (c) of profiles/gemm_mfma_shape_ab.md)"""
     rows = [("nt", n, M, N, K) for n, M, N, K in SHAPES[:4] + SHAPES[7:8] + SHAPES[10:14]]
     rows += [("nn", "dec gate_up dgrad", 8192, 3584, 37888), ("nn", "dec down dgrad", 8192, 18944, 3584), ("nn", "dec qkv dgrad", 8192, 3584, 4608),
              ("nn", "dec o dgrad", 8192, 3584, 3584), ("nn", "lm_head dgrad", 2048, 3584, 152064), ("nn", "enc fc1 dgrad", 12000, 1280, 5120), ("nn", "enc qkv dgrad", 12000, 1280, 3840),
              ("tn", "dec gate_up wgrad", 37888, 3584, 8192), ("tn", "dec down wgrad", 3584, 18944, 8192), ("tn", "dec qkv wgrad", 4608, 3584, 8192),
              ("tn", "dec o wgrad", 3584, 3584, 8192), ("tn", "lm_head wgrad", 152064, 3584, 2048), ("tn", "enc fc1 wgrad", 5120, 1280, 12000),
              ("tn", "enc qkv wgrad", 3840, 1280, 12000), ("tn", "enc out wgrad", 1280, 1280, 12000)]
+    return rows
+
+
+def libs_ab(other_path, out_path):
+    """per-shape A/B of two builds of libafk.so (profiles/gemm_tail.md table (b)): faster / slower only if the medians differ by more than twice the
+    larger (max - min) of the two arms, else a tie"""
+    import ctypes
+    import statistics
+    from audio_flamingo_amd import _lib
+    this = _lib.load()
+    other = ctypes.CDLL(other_path)
+    for name, (ret, argtypes, _) in _lib.prototypes().items():
+        fn = getattr(other, name)
+        fn.restype, fn.argtypes = ret, argtypes
+    arms = {"this": this, "other": other}
+    res = []
+    try:
+        for lib in arms.values():
+            _lib._lib = lib
+            ops.gemm_set_variant(2)
+        for form, name, M, N, K in step_rows():
+            a = torch.randn((K, M) if form == "tn" else (M, K), device=dev).to(torch.bfloat16)
+            b = torch.randn((N, K) if form == "nt" else (K, N), device=dev).to(torch.bfloat16)
+            c = torch.empty((M, N), device=dev, dtype=torch.bfloat16)
+            run = (lambda: ops.gemm_nt(a, b, out=c)) if form == "nt" else (lambda: ops.gemm(a, b, out=c, trans_a=form == "tn", trans_b=True))
+            ev = {k: [] for k in arms}
+            for it in range(30):          # 5 warm + 25 timed, the builds alternating launch by launch
+                for k, lib in arms.items():
+                    _lib._lib = lib
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(); run(); e1.record()
+                    if it >= 5:
+                        ev[k].append((e0, e1))
+            torch.cuda.synchronize()
+            row = {"form": form, "name": name, "M": M, "N": N, "K": K}
+            for k in arms:
+                us = sorted(1e3 * x.elapsed_time(y) for x, y in ev[k])
+                row[f"{k}_us"] = {"median": round(statistics.median(us), 1), "min": round(us[0], 1), "max": round(us[-1], 1)}
+            d = row["other_us"]["median"] - row["this_us"]["median"]
+            noise = 2 * max(row[f"{k}_us"]["max"] - row[f"{k}_us"]["min"] for k in arms)
+            row["this_vs_other_pct"] = round(100.0 * d / row["other_us"]["median"], 2)
+            row["verdict"] = "faster" if d > noise else "slower" if -d > noise else "tie"
+            res.append(row)
+            print(json.dumps(row), flush=True)
+            del a, b, c
+    finally:
+        for lib in arms.values():
+            _lib._lib = lib
+            ops.gemm_set_variant(0)
+        _lib._lib = this
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        json.dump({"device": torch.cuda.get_device_name(0), "this": _lib.LIB_PATH, "other": other_path, "rows": res}, open(out_path, "w"), indent=1)
+
+
+def mfma_ab(out_path):
+    """per-shape A/B of the MFMA shapes (profiles/gemm_mfma_shape_ab.md table (c))"""
+    import statistics
+    rows = step_rows()
     res = []
     ops.gemm_set_variant(2)
     try:
@@ -63,6 +123,9 @@ def mfma_ab(out_path):
         json.dump({"device": torch.cuda.get_device_name(0), "rows": res}, open(out_path, "w"), indent=1)
 
 
+if len(sys.argv) > 2 and sys.argv[1] == "libs":
+    libs_ab(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "mfma":
     mfma_ab(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
