@@ -29,6 +29,7 @@ __device__ long long* g_chain_stamps = nullptr;
 #endif
 
 #define AFK_CHAIN_BATCH_MAX 8
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;   // 16 bytes of FP8 codes
 enum { PRO_PLAIN = 0, PRO_RMS = 1, PRO_PLAIN_LDS = 2 };   // PRO_PLAIN_LDS (matrix-pipe form): input rows as they are, but loaded cooperatively and handed to the MFMA through the LDS strip like PRO_RMS
 enum { EPI_QKV = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_LOGITS = 3, EPI_RESID_NORM = 4 };
 
@@ -38,6 +39,9 @@ struct ChainArgs {
     float eps;
     const bf16* W;        // [N, K] row-major (nn.Linear layout)
     int64_t ldw;
+    const uint8_t* Wq;    // W8 (gemv_chain_kernel only): the weights as OCP e4m3fn codes [N][ld_wq] in place of W ...
+    int64_t ld_wq;
+    const float* wscale;  // ... and the fp32 scale of every output row [N]: row r of the Linear is wscale[r] * code
     int N, K;
     const bf16* bias;     // EPI_QKV
     const bf16* cos_t;    // [pos][D]
@@ -86,9 +90,20 @@ __device__ __forceinline__ float dot8(const bf16x8 a, const bf16x8 b, float acc)
 #else
 #define AFK_CHAIN_WPE_ATTR
 #endif
-template <int PRO, int EPI, int S, int R>
+//
+// W8 (generate(decode_weights="fp8"), decode_w8.py): the same kernel on FP8 weights - OCP e4m3fn codes with one fp32 scale per output row (afk_quantize_rows_fp8),
+// half the streamed bytes.  A 16-byte weight load then carries 16 elements, so a chunk is 1024 elements of K and a lane's slice of x (and of the norm weight)
+// two 16-byte loads; the bytes in flight per wave are what they were.  The codes are widened by v_cvt_pk_f32_fp8 (two per instruction) and multiplied in fp32
+// with v_pk_fma_f32 into a pair of sums per row: 8 + 8 VALU instructions per row and load, against 8 + 8 conversions to bf16 pairs in front of 8 v_dot2 for the
+// other candidate (fp8 -> f32 -> bf16 -> fdot2) - the ISA decided, the packed-fp32 form is a third shorter and rounds nothing.  x is widened once per chunk and
+// shared by the R rows.  The row scale multiplies the finished fp32 sum in front of the first bf16 rounding; everything behind it is the bf16 epilogue.
+template <int PRO, int EPI, int S, int R, bool W8 = false>
 __global__ __launch_bounds__(64 * (S > 4 ? S : 4)) AFK_CHAIN_WPE_ATTR void gemv_chain_kernel(ChainArgs p, int ngroups) {
     constexpr int G = S >= 4 ? 1 : 4 / S;   // groups per block
+    constexpr int VE = W8 ? 16 : 8;         // elements of K per lane and chunk = one 16-byte weight load
+    constexpr int CSH = W8 ? 10 : 9;        // log2 of a chunk's elements
+    using WT = std::conditional_t<W8, uint8_t, bf16>;
+    using WV = std::conditional_t<W8, u32x4, bf16x8>;
     constexpr int HR = R / 2;
     constexpr int LPR = 64 / R;             // after the reduce-scatter lane LPR * j holds row j
     __shared__ float red[G][S][R];
@@ -123,8 +138,9 @@ __global__ __launch_bounds__(64 * (S > 4 ? S : 4)) AFK_CHAIN_WPE_ATTR void gemv_
     // them, bias -> position -> cos / sin were three dependent round trips at the tail of a 10 us kernel)
     const int er = lane & (R - 1);
     const int erow = er < HR ? rA + er : rB + er - HR;
-    float e_bias = 0.f, e_cos = 0.f, e_sin = 0.f, e_res = 0.f;
+    float e_bias = 0.f, e_cos = 0.f, e_sin = 0.f, e_res = 0.f, e_scale = 1.f;
     int e_start = 0;
+    if constexpr (W8) e_scale = p.wscale[erow];
     if (EPI == EPI_QKV) {
         e_bias = (float)p.bias[erow];
         e_start = *p.start;
@@ -136,10 +152,15 @@ __global__ __launch_bounds__(64 * (S > 4 ? S : 4)) AFK_CHAIN_WPE_ATTR void gemv_
     } else if (EPI == EPI_RESID) {
         e_res = (float)p.residual[erow];
     }
-    const bf16* wrow[R];
+    const WT* wrow[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) wrow[r] = p.W + (int64_t)(r < HR ? rA + r : rB + r - HR) * p.ldw;
-    const int nch = (p.K + 511) >> 9;
+    for (int r = 0; r < R; ++r) {
+        const int64_t row = r < HR ? rA + r : rB + r - HR;
+        if constexpr (W8) wrow[r] = p.Wq + row * p.ld_wq;
+        else wrow[r] = p.W + row * p.ldw;
+    }
+    const int nch = (p.K + (1 << CSH) - 1) >> CSH;
+    const int nchx = (p.K + 511) >> 9;   // the statistic's passes over x: 512 elements each, whatever a weight chunk holds
     // PRO_RMS: the whole input row FIRST (L2 / HBM latency of a row another XCD has just written) - loads return in order, so requested behind the weight
     // chunks the row would arrive behind them and the statistic, the normalisation and every dot product would start when the last weight byte is in
     constexpr int XCH = 8;   // row chunks held in registers for the statistic (K <= 4096); longer rows: a second pass below
@@ -158,24 +179,31 @@ __global__ __launch_bounds__(64 * (S > 4 ? S : 4)) AFK_CHAIN_WPE_ATTR void gemv_
     }
     // a chunk = its slice of x (and of the norm weight) and R weight vectors; x is requested ahead of the weights for the same reason as above
     struct Chunk {
-        bf16x8 x, nw, w[R];
+        bf16x8 x[VE / 8], nw[VE / 8];
+        WV w[R];
     };
     auto load_chunk = [&](Chunk& dst, int c) {
-        const int k = (c << 9) + lane * 8;
-        const bool ok = k < p.K;
+        const int k = (c << CSH) + lane * VE;
+        const bool ok = k < p.K;     // W8: K % 16 == 0, a lane's 16 elements lie inside the row or behind it as one
         const int kk = ok ? k : 0;   // masked lanes re-read the row's first vector (valid memory); their x is zeroed
-        dst.x = *(const bf16x8*)(p.x + kk);
-        if (PRO == PRO_RMS) dst.nw = *(const bf16x8*)(p.normw + kk);
-        if (!ok) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) dst.x[e] = (bf16)0.f;
+        for (int h = 0; h < VE / 8; ++h) {
+            dst.x[h] = *(const bf16x8*)(p.x + kk + 8 * h);
+            if (PRO == PRO_RMS) dst.nw[h] = *(const bf16x8*)(p.normw + kk + 8 * h);
+            if (!ok) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) dst.x[h][e] = (bf16)0.f;
+            }
         }
 #pragma unroll
-        for (int r = 0; r < R; ++r) dst.w[r] = __builtin_nontemporal_load((const bf16x8*)(wrow[r] + kk));   // streamed once
+        for (int r = 0; r < R; ++r) dst.w[r] = __builtin_nontemporal_load((const WV*)(wrow[r] + kk));   // streamed once
     };
     float acc[R];
+    f32x2 acc2[W8 ? R : 1];   // W8: the sums of the even and of the odd elements of a row (v_pk_fma_f32), added once behind the K loop
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int r = 0; r < (W8 ? R : 1); ++r) acc2[r] = f32x2{0.f, 0.f};
     Chunk q0, q1;
     const int c = ks;
     if (live && c < nch) load_chunk(q0, c);   // two chunks deep in flight while the row statistic below is computed
@@ -189,7 +217,7 @@ __global__ __launch_bounds__(64 * (S > 4 ? S : 4)) AFK_CHAIN_WPE_ATTR void gemv_
         for (int cc = 0; cc < XCH; ++cc)
 #pragma unroll
             for (int e = 0; e < 8; ++e) ss += (float)xs[cc][e] * (float)xs[cc][e];
-        for (int cc = XCH; cc < nch; ++cc) {
+        for (int cc = XCH; cc < nchx; ++cc) {
             const int k = (cc << 9) + lane * 8;
             if (k < p.K) {
                 const bf16x8 xv = *(const bf16x8*)(p.x + k);
@@ -202,13 +230,31 @@ __global__ __launch_bounds__(64 * (S > 4 ? S : 4)) AFK_CHAIN_WPE_ATTR void gemv_
     }
     AFK_STAMP(1);
     auto fma_chunk = [&](const Chunk& q) {
-        bf16x8 xv = q.x;
-        if (PRO == PRO_RMS) {
+        bf16x8 xv[VE / 8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) xv[e] = (bf16)((float)q.nw[e] * rbf((float)xv[e] * rstd));   // x = 0 on masked lanes -> h = 0
+        for (int h = 0; h < VE / 8; ++h) {
+            xv[h] = q.x[h];
+            if (PRO == PRO_RMS) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) xv[h][e] = (bf16)((float)q.nw[h][e] * rbf((float)xv[h][e] * rstd));   // x = 0 on masked lanes -> h = 0
+            }
         }
+        if constexpr (W8) {
+            f32x2 xf[8];   // the lane's 16 inputs, widened once for the R rows
 #pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = dot8(q.w[r], xv, acc[r]);
+            for (int j = 0; j < 8; ++j) xf[j] = f32x2{(float)xv[j >> 2][2 * (j & 3)], (float)xv[j >> 2][2 * (j & 3) + 1]};
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {   // a 32-bit word = four codes, widened two at a time
+                    const uint32_t u = q.w[r][j];
+                    acc2[r] = __builtin_elementwise_fma(__builtin_amdgcn_cvt_pk_f32_fp8(u, false), xf[2 * j], acc2[r]);
+                    acc2[r] = __builtin_elementwise_fma(__builtin_amdgcn_cvt_pk_f32_fp8(u, true), xf[2 * j + 1], acc2[r]);
+                }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc[r] = dot8(q.w[r], xv[0], acc[r]);
+        }
     };
     if (live) {
         for (int cc = c; cc < nch; cc += 2 * S) {
@@ -220,6 +266,10 @@ __global__ __launch_bounds__(64 * (S > 4 ? S : 4)) AFK_CHAIN_WPE_ATTR void gemv_
                 if (cc + 3 * S < nch) load_chunk(q1, cc + 3 * S);
             }
         }
+    }
+    if constexpr (W8) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = acc2[r][0] + acc2[r][1];
     }
     // ---- cross-lane reduce-scatter of the R per-lane sums (R - 1 exchanges, then plain halvings): lane LPR * j ends up with row j
     {
@@ -251,6 +301,7 @@ __global__ __launch_bounds__(64 * (S > 4 ? S : 4)) AFK_CHAIN_WPE_ATTR void gemv_
     float tot = 0.f;
 #pragma unroll
     for (int q = 0; q < S; ++q) tot += red[gi][q][er];
+    if constexpr (W8) tot *= e_scale;   // the row's scale on the finished fp32 sum, in front of the first bf16 rounding
     if (EPI == EPI_QKV) {
         const float mine = rbf(tot + e_bias);
         const float other = __shfl_xor(mine, HR, 64);
@@ -1159,7 +1210,7 @@ int chain_knob(int which, int dflt, bool is_r) {   // read per launch (a getenv;
     return (s == 1 || s == 2 || s == 4 || s == 8) ? s : dflt;
 }
 
-template <int PRO, int EPI>
+template <int PRO, int EPI, bool W8 = false>
 int launch_chain(const ChainArgs& p, int rows, int which, int S_dflt, int R_dflt, bool r4_ok, hipStream_t st) {
     const int S = chain_knob(which, S_dflt, false);
     int R_ = chain_knob(which, R_dflt, true);
@@ -1168,7 +1219,7 @@ int launch_chain(const ChainArgs& p, int rows, int which, int S_dflt, int R_dflt
 #define AFK_CHAIN(S_, R__)                                                                                                                          \
     {                                                                                                                                               \
         constexpr int G_ = S_ >= 4 ? 1 : 4 / S_;                                                                                                    \
-        hipLaunchKernelGGL((gemv_chain_kernel<PRO, EPI, S_, R__>), dim3((unsigned)afk_cdiv(ngroups, G_)), dim3(64 * (S_ > 4 ? S_ : 4)), 0, st, p,   \
+        hipLaunchKernelGGL((gemv_chain_kernel<PRO, EPI, S_, R__, W8>), dim3((unsigned)afk_cdiv(ngroups, G_)), dim3(64 * (S_ > 4 ? S_ : 4)), 0, st, p, \
                            ngroups);                                                                                                                \
     }
 #define AFK_CHAIN_R(S_)                 \
@@ -1312,6 +1363,63 @@ extern "C" int afk_decode_chain_lm_head(const void* x, const void* norm_w, float
     p.part_val = part_val; p.part_idx = part_idx;
     launch_chain<PRO_RMS, EPI_LOGITS>(p, N, 4, N / 8 >= 2048 ? 1 : 4, 8, false, ST);   // always eight rows per group: part_* are indexed by it
     AFK_LAUNCH_CHECK("afk_decode_chain_lm_head");
+    return AFK_OK;
+}
+
+// ---------------------------------------------------------------- the same four launches on FP8 weights (W8: e4m3fn codes + one fp32 scale per output row)
+// what the bf16 entries ask of W / ldw, asked of the codes: a lane's load is 16 bytes = 16 elements
+#define AFK_W8_REQUIRE(name, Wq, ldq, wscale, K)                                                                                            \
+    AFK_REQUIRE((Wq) && (wscale) && (K) > 0 && (K) % 16 == 0 && (ldq) >= (K) && (ldq) % 16 == 0 && ((uintptr_t)(Wq) & 15) == 0,             \
+                name ": FP8 weights need K %% 16 == 0, ldq %% 16 == 0, 16-byte-aligned rows and a scale per row")
+
+extern "C" int afk_decode_chain_qkv_w8(const void* x, const void* norm_w, float eps, const void* Wq, int64_t ldq, const float* wscale, int K, const void* bias,
+                                       const void* cos_t, const void* sin_t, const int* pos, void* q_out, void* kcache, void* vtcache, int spad,
+                                       const int* start_dev, int Hq, int Hkv, int D, void* stream) {
+    AFK_REQUIRE(x && norm_w && Wq && wscale && bias && cos_t && sin_t && pos && q_out && kcache && vtcache && start_dev, "afk_decode_chain_qkv_w8: null pointer");
+    AFK_W8_REQUIRE("afk_decode_chain_qkv_w8", Wq, ldq, wscale, K);
+    AFK_REQUIRE(Hq > 0 && Hkv > 0 && D % 16 == 0 && spad > 0, "afk_decode_chain_qkv_w8: unsupported shape (head_dim %% 16 == 0)");
+    ChainArgs p = {};
+    p.x = (const bf16*)x; p.normw = (const bf16*)norm_w; p.eps = eps; p.Wq = (const uint8_t*)Wq; p.ld_wq = ldq; p.wscale = wscale; p.N = (Hq + 2 * Hkv) * D; p.K = K;
+    p.bias = (const bf16*)bias; p.cos_t = (const bf16*)cos_t; p.sin_t = (const bf16*)sin_t; p.pos = pos; p.start = start_dev; p.q_out = (bf16*)q_out;
+    p.Kc = (bf16*)kcache; p.Vt = (bf16*)vtcache; p.spad = spad; p.Hq = Hq; p.Hkv = Hkv; p.D = D;
+    launch_chain<PRO_RMS, EPI_QKV, true>(p, p.N, 0, 4, 8, true, ST);
+    AFK_LAUNCH_CHECK("afk_decode_chain_qkv_w8");
+    return AFK_OK;
+}
+
+extern "C" int afk_decode_chain_linear_residual_w8(const void* x, const void* Wq, int64_t ldq, const float* wscale, int N, int K, const void* residual, void* out,
+                                                   void* stream) {
+    AFK_REQUIRE(x && residual && out && N > 0 && N % 8 == 0, "afk_decode_chain_linear_residual_w8: bad arguments (N %% 8 == 0)");
+    AFK_W8_REQUIRE("afk_decode_chain_linear_residual_w8", Wq, ldq, wscale, K);
+    ChainArgs p = {};
+    p.x = (const bf16*)x; p.Wq = (const uint8_t*)Wq; p.ld_wq = ldq; p.wscale = wscale; p.N = N; p.K = K; p.residual = (const bf16*)residual; p.out = (bf16*)out; p.D = 2;
+    launch_chain<PRO_PLAIN, EPI_RESID, true>(p, N, K > 4096 ? 2 : 1, K > 4096 ? 8 : 4, 8, true, ST);
+    AFK_LAUNCH_CHECK("afk_decode_chain_linear_residual_w8");
+    return AFK_OK;
+}
+
+extern "C" int afk_decode_chain_gate_up_w8(const void* x, const void* norm_w, float eps, const void* Wq, int64_t ldq, const float* wscale, int I, int K,
+                                           void* act_out, void* stream) {
+    AFK_REQUIRE(x && norm_w && act_out && I > 0 && I % 4 == 0, "afk_decode_chain_gate_up_w8: unsupported shape (I %% 4 == 0)");
+    AFK_W8_REQUIRE("afk_decode_chain_gate_up_w8", Wq, ldq, wscale, K);
+    ChainArgs p = {};
+    p.x = (const bf16*)x; p.normw = (const bf16*)norm_w; p.eps = eps; p.Wq = (const uint8_t*)Wq; p.ld_wq = ldq; p.wscale = wscale; p.N = 2 * I; p.K = K;
+    p.out = (bf16*)act_out; p.D = 2;
+    launch_chain<PRO_RMS, EPI_SWIGLU, true>(p, 2 * I, 3, I / 4 >= 2048 ? 1 : 4, 8, true, ST);
+    AFK_LAUNCH_CHECK("afk_decode_chain_gate_up_w8");
+    return AFK_OK;
+}
+
+extern "C" int afk_decode_chain_lm_head_w8(const void* x, const void* norm_w, float eps, const void* Wq, int64_t ldq, const float* wscale, int N, int K,
+                                           float* logits, float* part_val, int* part_idx, void* stream) {
+    AFK_REQUIRE(x && norm_w && N > 0 && N % 8 == 0, "afk_decode_chain_lm_head_w8: unsupported shape (N %% 8 == 0)");
+    AFK_W8_REQUIRE("afk_decode_chain_lm_head_w8", Wq, ldq, wscale, K);
+    AFK_REQUIRE((logits || part_val) && (!part_val == !part_idx), "afk_decode_chain_lm_head_w8: logits and / or both partial-argmax buffers");
+    ChainArgs p = {};
+    p.x = (const bf16*)x; p.normw = (const bf16*)norm_w; p.eps = eps; p.Wq = (const uint8_t*)Wq; p.ld_wq = ldq; p.wscale = wscale; p.N = N; p.K = K;
+    p.out_f32 = logits; p.D = 2; p.part_val = part_val; p.part_idx = part_idx;
+    launch_chain<PRO_RMS, EPI_LOGITS, true>(p, N, 4, N / 8 >= 2048 ? 1 : 4, 8, false, ST);   // always eight rows per group: part_* are indexed by it
+    AFK_LAUNCH_CHECK("afk_decode_chain_lm_head_w8");
     return AFK_OK;
 }
 

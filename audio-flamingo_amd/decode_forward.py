@@ -10,6 +10,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib, ops
+from . import decode_w8 as _w8mod
 from ._lib import AfkError
 from .generation import continuation_lengths, continuation_mask_check
 
@@ -124,6 +125,9 @@ class AfkDecodeForwardMixin:
     decode_prologue_max = int(os.environ.get("AFK_DECODE_PROLOGUE_MAX", "8"))   # largest batch that takes the RMSNorm in the consumer's prologue (above: a norm launch + plain launches)
     decode_norm_mode = os.environ.get("AFK_DECODE_NORM", "prologue")   # batched decode, four sequences and more: "prologue" | "producer" | "launch" (_decode_layers_chain_batched)
     decode_chain_batch = int(os.environ.get("AFK_DECODE_CHAIN_BATCH", "8"))   # largest batch the one-launch-per-Linear kernels take (0: single sequence only)
+    decode_weight_dtype = os.environ.get("AFK_DECODE_WEIGHTS", "bf16")   # generate(decode_weights=None): "bf16" | "fp8" - the single-sequence chain on the FP8 copy of its weights (decode_w8.py)
+    _w8 = None   # the FP8 copy (decode_w8.DecodeW8): built by quantize_decode_weights() / the first fp8 call, None until then and after drop_decode_weights()
+    last_w8_stats = None   # the last generate() call that decoded on the FP8 copy: decode_w8.stats; None after every other call
     decode_splits = 8  # key-range splits of the Q = 1 attention (0: use the interval MFMA kernel instead)
     decode_fused_glue = True  # B <= 4: one glue kernel per Linear (csrc/decode_glue.hip) instead of reduce / bias / rope / append / norm / SwiGLU launches
     cache_headroom = 256  # forward(use_cache=True): positions reserved beyond the prompt; the cache grows by doubling when they run out
@@ -357,13 +361,49 @@ class AfkDecodeForwardMixin:
             _lib.call("afk_decode_residual_rmsnorm", ws.data_ptr(), sp, B, H, x2.data_ptr(), self._next_norm_weight(i).data_ptr(), eps, x.data_ptr(), h.data_ptr(), st)
         return h  # already through the final norm
 
-    def _chain_layers(self, x, cache, pos_rows, krange, start_dev, aws=None):
+    # ------------------------------------------------------------------ FP8 decode weights (decode_w8.py)
+    def quantize_decode_weights(self):
+        """build (or rebuild) the FP8 copy of the decoder Linears and the lm_head that generate(decode_weights="fp8") decodes on -> the decode_w8.DecodeW8 record
+        (per layer a uint8 code tensor and an fp32 scale vector for qkv / o_proj / gate_up / down_proj, the same for lm_head.weight, and the arena.version() they
+        were taken at).  Extra memory: the bf16 weights stay (the prefill and forward() read them)."""
+        self._require_hip()
+        self._w8 = _w8mod.build(self)
+        return self._w8
+
+    def drop_decode_weights(self):
+        """free the FP8 copy (the next fp8 call builds it again)"""
+        self._w8 = None
+
+    def _w8_current(self):
+        """the FP8 copy of the weights AS THEY ARE: built on first use, rebuilt whenever arena.version() has moved (load_state_dict, in-place torch writes, the
+        optimizer's raw-pointer steps - the rule of the W^T shadows); leaves the call's last_w8_stats"""
+        rebuilt = self._w8 is None or self._w8.version != self.arena.version()
+        if rebuilt:
+            self.quantize_decode_weights()
+        self.last_w8_stats = _w8mod.stats(self._w8, rebuilt)
+        return self._w8
+
+    def _w8_resolve(self, decode_weights, rows, num_beams, copies, guidance, lookup, share_prompt, use_cache, exact_fp32):
+        """decode_w8.resolve with what only the model knows: the geometry"""
+        on = (self.decode_weight_dtype if decode_weights is None else decode_weights) == "fp8"
+        chain_ok = widths_ok = head_ok = True
+        if on:   # asked only where the answer is read: with the switch off the call reads no attribute it did not read before
+            chain_ok = self._chain_ok(1)
+            widths_ok = self.H % 16 == 0 and (self.Hq * self.D) % 16 == 0 and self.I % 16 == 0
+            head_ok = self.arena["lm_head.weight"].data.shape[0] % 8 == 0
+        return _w8mod.resolve(decode_weights, self.decode_weight_dtype, rows=rows, num_beams=num_beams, copies=copies, guidance=guidance, lookup=lookup,
+                              share_prompt=share_prompt, use_cache=use_cache, exact_fp32=exact_fp32, chain_ok=chain_ok, widths_ok=widths_ok, head_ok=head_ok)
+
+    def _chain_layers(self, x, cache, pos_rows, krange, start_dev, aws=None, w8=None):
         """one new position of ONE sequence: five launches per decoder layer (round 4; ten on the split-K + glue path above).  Every Linear is one
         weight-streaming launch in which a group of waves owns eight complete output rows: the qkv launch normalises the residual stream in its prologue
         and applies bias / RoPE / cache append in its epilogue, o_proj and down_proj add the residual, gate|up normalises in its prologue and multiplies
         silu(gate) * up in its epilogue; the Q = 1 attention merges its key chunks in the last block to finish (afk_attn_decode_fused).  -> the residual row
-        behind the last layer, NOT through the final RMSNorm (_chain_lm_head takes it in its prologue)"""
+        behind the last layer, NOT through the final RMSNorm (_chain_lm_head takes it in its prologue).
+        w8 (a decode_w8.DecodeW8): the four Linears stream its FP8 codes and row scales (afk_decode_chain_*_w8) in place of the bf16 weights; nothing else differs"""
         g, w = CacheGeometry.of(self, cache), self._w
+        if w8 is not None:
+            return self._chain_layers_w8(g, x, pos_rows, krange, start_dev, aws, w8)
         Hq, Hkv, D, H, nq, eps, st, dev = g.Hq, g.Hkv, g.D, g.H, g.nq, g.eps, g.stream, x.device
         if aws is None:
             aws = self._decode_attn_workspace(dev, g.Spad)
@@ -388,18 +428,50 @@ class AfkDecodeForwardMixin:
             _lib.call("afk_decode_chain_linear_residual", act.data_ptr(), wd.data_ptr(), wd.stride(0), H, I, x2.data_ptr(), x.data_ptr(), st)
         return x
 
-    def _chain_lm_head(self, x, head, logits=None, part_val=None, part_idx=None):
+    def _chain_layers_w8(self, g, x, pos_rows, krange, start_dev, aws, w8):
+        """_chain_layers on the FP8 copy: the same five launches per layer, the Linears' weight pointer and pitch replaced by codes, pitch and row scales"""
+        w = self._w
+        Hq, Hkv, D, H, nq, eps, st, dev = g.Hq, g.Hkv, g.D, g.H, g.nq, g.eps, g.stream, x.device
+        if aws is None:
+            aws = self._decode_attn_workspace(dev, g.Spad)
+        ns = self._decode_attn_ws_check(aws, 1, g.Spad)
+        q = torch.empty((1, nq), device=dev, dtype=torch.bfloat16)
+        o = torch.empty((1, nq), device=dev, dtype=torch.bfloat16)
+        q8 = lambda t: (t.codes.data_ptr(), t.codes.stride(0), t.scale.data_ptr())
+        for i in range(g.L):
+            lw = w8.layers[i]
+            _lib.call("afk_decode_chain_qkv_w8", x.data_ptr(), w(i, "input_layernorm.weight").data_ptr(), eps, *q8(lw["self_attn.qkv.weight"]), H,
+                      w(i, "self_attn.qkv.bias").data_ptr(), g.cos.data_ptr(), g.sin.data_ptr(), pos_rows.data_ptr(), q.data_ptr(), g.k(i), g.vt(i), g.vt_row, start_dev.data_ptr(), Hq, Hkv, D, st)
+            _lib.call("afk_attn_decode_fused", q.data_ptr(), nq, D, g.k(i), g.k_sample, g.k_row, D, g.vt(i), g.vt_sample, g.vt_row,
+                      o.data_ptr(), nq, D, krange.data_ptr(), 1, Hq, Hkv, D, float(D ** -0.5), ns, aws.data_ptr(), st)
+            x2 = torch.empty_like(x)
+            _lib.call("afk_decode_chain_linear_residual_w8", o.data_ptr(), *q8(lw["self_attn.o_proj.weight"]), H, nq, x.data_ptr(), x2.data_ptr(), st)
+            gu = lw["mlp.gate_up.weight"]
+            I = gu.codes.shape[0] // 2
+            act = torch.empty((1, I), device=dev, dtype=torch.bfloat16)
+            _lib.call("afk_decode_chain_gate_up_w8", x2.data_ptr(), w(i, "post_attention_layernorm.weight").data_ptr(), eps, *q8(gu), I, H, act.data_ptr(), st)
+            x = torch.empty_like(x2)
+            _lib.call("afk_decode_chain_linear_residual_w8", act.data_ptr(), *q8(lw["mlp.down_proj.weight"]), H, I, x2.data_ptr(), x.data_ptr(), st)
+        return x
+
+    def _chain_lm_head(self, x, head, logits=None, part_val=None, part_idx=None, w8=None):
         """the final RMSNorm + lm_head (rows % 8 == 0) on the residual row of _chain_layers, one more launch of the same kind: it leaves the fp32 logits [1, V]
-        and / or (max, argmax) per eight rows, whichever buffers are given"""
+        and / or (max, argmax) per eight rows, whichever buffers are given.  w8: on the FP8 copy of the lm_head (afk_decode_chain_lm_head_w8)"""
+        if w8 is not None:
+            h8 = w8.head
+            _lib.call("afk_decode_chain_lm_head_w8", x.data_ptr(), self.arena[self._lm + "norm.weight"].data.data_ptr(), float(self.rms_eps), h8.codes.data_ptr(),
+                      h8.codes.stride(0), h8.scale.data_ptr(), h8.codes.shape[0], x.shape[1], ops._p(logits), ops._p(part_val), ops._p(part_idx), ops._stream())
+            return
         _lib.call("afk_decode_chain_lm_head", x.data_ptr(), self.arena[self._lm + "norm.weight"].data.data_ptr(), float(self.rms_eps), head.data_ptr(), head.stride(0),
                   head.shape[0], x.shape[1], ops._p(logits), ops._p(part_val), ops._p(part_idx), ops._stream())
 
-    def _decode_layers_chain(self, x, cache, pos_rows, krange, start_dev, aws=None, head=None):
-        """_chain_layers, then with `head` (lm_head weight, rows % 8 == 0) the fp32 logits [1, V] of _chain_lm_head; otherwise the normalised hidden row"""
-        x = self._chain_layers(x, cache, pos_rows, krange, start_dev, aws=aws)
+    def _decode_layers_chain(self, x, cache, pos_rows, krange, start_dev, aws=None, head=None, w8=None):
+        """_chain_layers, then with `head` (lm_head weight, rows % 8 == 0) the fp32 logits [1, V] of _chain_lm_head; otherwise the normalised hidden row.
+        w8: both on the FP8 copy (generate() resolved that the head has its rows % 8 == 0)"""
+        x = self._chain_layers(x, cache, pos_rows, krange, start_dev, aws=aws, w8=w8)
         if head is not None:
             logits = torch.empty((1, head.shape[0]), device=x.device, dtype=torch.float32)
-            self._chain_lm_head(x, head, logits=logits)
+            self._chain_lm_head(x, head, logits=logits, w8=w8)
             return logits
         return ops.rmsnorm_fwd(x, self.arena[self._lm + "norm.weight"].data, self.rms_eps)[0]
 
@@ -541,7 +613,7 @@ class AfkDecodeForwardMixin:
             if st.aws is None:
                 st.aws = self._decode_attn_workspace(x.device, st.cache[1].shape[4])
             head = st.head if st.head.shape[0] % 8 == 0 else None
-            y = self._decode_layers_chain(x.contiguous(), st.cache, pos1, kr1, st.cur, aws=st.aws, head=head)
+            y = self._decode_layers_chain(x.contiguous(), st.cache, pos1, kr1, st.cur, aws=st.aws, head=head, w8=st.w8)
             if head is not None:
                 return y
         elif self.decode_fused_glue and B <= ops.GEMV_MAX_M and self.D in (64, 128) and self.decode_splits > 0 and ops.SPLITK:

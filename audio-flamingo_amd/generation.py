@@ -18,6 +18,7 @@ from . import decode_lookup as _lookup
 from . import decode_process as _process
 from . import decode_share as _share
 from . import decode_stop as _stop
+from . import decode_w8 as _w8mod
 from ._lib import AfkError
 
 
@@ -58,6 +59,7 @@ class DecodeState:
     single: Optional[SingleSequence] = None
     on_device: Optional[OnDevice] = None
     shared: Optional[_share.SharedPrompt] = None   # the prompt cache of a call that shares it (decode_share.py): `cache` is then the TAIL cache, cur counts its slots from 0
+    w8: Optional[_w8mod.DecodeW8] = None   # FP8 decode weights (decode_w8.py): the single-sequence chain streams this copy of its Linears and of the lm_head
     cfg: Optional[_cfg.CfgState] = None   # classifier-free guidance (decode_cfg.py): cache, lo and nxt have 2 * B rows - [0, B) conditional, [B, 2B) unconditional - and everything else B
 
 
@@ -206,7 +208,7 @@ class AfkGenerationMixin:
         if st.sampling or st.proc:
             # sampled, or logits processors: the lm_head launch writes the fp32 logits; the processors' launch edits the row (and, greedy, selects from it and
             # does the bookkeeping); the sample launch draws and does the bookkeeping
-            self._chain_lm_head(x, st.head, logits=od.logits)
+            self._chain_lm_head(x, st.head, logits=od.logits, w8=st.w8)
             select = {} if st.sampling else dict(select=True, **book)   # greedy: st.proc is set here
             self._record_and_process(st, od.logits, step_base=st.cur, step_off=off, **select)
             if select:
@@ -218,7 +220,7 @@ class AfkGenerationMixin:
             return
         # plain greedy: the lm_head launch leaves (max, argmax) per eight rows, the select launch does everything up to the next step.  Flags off: no logits
         # row is written; on: the same launch also leaves the row (the partial argmax pairs, hence the ids, are the same)
-        self._chain_lm_head(x, st.head, logits=od.logits if rec else None, part_val=od.part_val, part_idx=od.part_idx)
+        self._chain_lm_head(x, st.head, logits=od.logits if rec else None, part_val=od.part_val, part_idx=od.part_idx, w8=st.w8)
         if rec:   # no processor: scores and logits are the same rows (one buffer when both are asked for); in front of the select launch, which advances cur
             self._record_rows(rec, "logits", od.logits, step_base=st.cur, step_off=off)
             self._record_rows(rec, "scores", od.logits, step_base=st.cur, step_off=off)
@@ -228,7 +230,7 @@ class AfkGenerationMixin:
     def _decode_step(self, st):
         """one greedy or sampled decode step on static buffers (everything position-dependent lives on the device): HIP-graph capturable"""
         if st.on_device is not None:   # one sequence: 5 launches per layer + lm_head + ONE launch for argmax or the draw / token / positions / the next embedding row
-            x = self._chain_layers(st.on_device.x0, st.cache, st.single.pos1, st.single.kr1, st.cur, aws=st.aws)
+            x = self._chain_layers(st.on_device.x0, st.cache, st.single.pos1, st.single.kr1, st.cur, aws=st.aws, w8=st.w8)
             self._select_on_device(st, x)
             if st.stop:   # behind the selection launch, which has advanced cur (= state[2]) already: one step back.  The next embedding row is in x0: no pad is fed
                 _stop.apply(st.stop, st.nxt, step_base=st.cur, step_off=st.tok_off - 1)
@@ -369,7 +371,7 @@ class AfkGenerationMixin:
                  no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, min_p=None, typical_p=1.0,
                  epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, sequence_bias=None, bad_words_ids=None, min_length=0,
                  forced_eos_token_id=None, exponential_decay_length_penalty=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, share_prompt=None,
-                 guidance_scale=None, negative_prompt_ids=None, negative_prompt_attention_mask=None, **kwargs):
+                 guidance_scale=None, negative_prompt_ids=None, negative_prompt_attention_mask=None, decode_weights=None, **kwargs):
         """Greedy decoding, sampling or beam search on a KV cache, with GenerationMixin.generate's arguments and results; docs/generate.md describes every
         route, what it launches and how it differs from the reference.
 
@@ -406,6 +408,10 @@ class AfkGenerationMixin:
         row (the negative prompt, text only, its own cache rows, the same selected tokens) in the same decode step - one pass over the weights for both -
         and afk_decode_cfg replaces the row's logits by scale * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond) in front of every
         processor; `logits` keeps the raw conditional rows, past_key_values the conditional cache.  docs/generate.md, "Classifier-free guidance".
+        decode_weights (None: the class attribute decode_weight_dtype, env AFK_DECODE_WEIGHTS, default "bf16"): "fp8" - the decode steps of ONE sequence stream
+        an FP8 copy of the decoder Linears and the lm_head (OCP e4m3fn codes, one power-of-two scale per output row: half the bytes; decode_w8.py), built on
+        first use and rebuilt when the weights have changed.  Weights only: the prefill, the activations and the cache are what they are, and the decode logits
+        differ from the bf16 route by the quantisation.  "bf16": not one launch or allocation differs.  docs/generate.md, "FP8 decode weights".
         generation_config (default: self.generation_config if there is one) supplies every argument left at its default.
 
         Returns the ids [B * num_return_sequences, S0 + n]: the prompt, then the new tokens, pad_token_id behind a row's end.
@@ -420,9 +426,11 @@ class AfkGenerationMixin:
         with use_cache=False, AFK_EXACT_FP32=1, past_key_values, the per-step hooks, prompt-lookup decoding, the host beam loop or a geometry outside the
         batched decode chain (decode_share.resolve); guidance_scale with num_beams > 1, use_cache=False, AFK_EXACT_FP32=1, prompt-lookup decoding,
         past_key_values or share_prompt=True, with a negative prompt that holds the audio id or a negative mask that is not left padding (AfkError), with
-        negative_prompt_ids of another batch size or a mask of another shape (ValueError) (decode_cfg.resolve)."""
+        negative_prompt_ids of another batch size or a mask of another shape (ValueError) (decode_cfg.resolve); decode_weights="fp8" with more than one
+        row, num_beams > 1, num_return_sequences > 1, guidance_scale, prompt-lookup decoding, share_prompt=True, use_cache=False, AFK_EXACT_FP32=1 or a
+        geometry the single-sequence chain or its FP8 launches do not take (AfkError), any other value (ValueError) (decode_w8.resolve)."""
         self._require_hip()
-        self.last_share_stats = self.last_cfg_stats = None
+        self.last_share_stats = self.last_cfg_stats = self.last_w8_stats = None
         procs, criteria, streamer = kwargs.pop("logits_processor", None), kwargs.pop("stopping_criteria", None), kwargs.pop("streamer", None)
         out_kw = {k: kwargs.pop(k, None) for k in ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")}
         stop_strings, tokenizer = kwargs.pop("stop_strings", None), kwargs.pop("tokenizer", None) or None
@@ -476,6 +484,9 @@ class AfkGenerationMixin:
                                  stop_strings=bool(stop_spec.stop_strings), output_object=flags.return_dict)
         # the shared prompt cache: keyword, else the class attribute; None: off or nothing to share, and nothing below changes
         share = self._share_resolve(share_prompt, input_ids.shape[0], n_ret, int(num_beams), bool(use_cache), _exact.ENABLED, past is not None, hooks, lookup is not None, len(eos))
+        # FP8 decode weights: keyword, else the class attribute; False: today's route, and nothing below changes
+        fp8 = self._w8_resolve(decode_weights, input_ids.shape[0] * (n_ret if int(num_beams) == 1 else 1), int(num_beams), n_ret, cfg is not None, lookup is not None,
+                               share_prompt, bool(use_cache), _exact.ENABLED)
         if spec.active and (num_beams > 1 or not use_cache):
             raise AfkError("generate(repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens / sequence_bias / "
                            "bad_words_ids / min_length / forced_eos_token_id / exponential_decay_length_penalty): greedy or sampled decoding on the KV cache "
@@ -566,6 +577,8 @@ class AfkGenerationMixin:
         if guide is not None:   # both rows of a pair are fed the token; the slots count from where both prompts end
             tok0, cur0 = torch.cat([tok0, tok0]), guide.Smax
         st = self._new_state((Kc, Vt), lo, cur0, tok0, sampling=sampling, tok_off=1 - cur0, proc=proc, rec=rec, shared=shared, cfg=guide)   # the first token is draw 0
+        if fp8:   # the copy of the weights as they are now (built or rebuilt here, outside every capture); the steps below read it through st.w8
+            st.w8 = self._w8_current()
         sel = (lambda: st.nxt) if guide is None else (lambda: st.nxt[:B])   # the tokens of the B selected rows
         stop = None
         if stop_spec.device:   # more than one eos id, or stop strings: the rule is a launch of the step.  Token 0, eagerly, with the kernel of the captured steps

@@ -412,6 +412,23 @@ int afk_decode_chain_gate_up(const void* x, const void* norm_w, float eps, const
  * greedy selection GenerationMixin._sample does with torch.argmax (transformers/generation/utils.py:2790).  N % 8 == 0, K % 8 == 0. */
 int afk_decode_chain_lm_head(const void* x, const void* norm_w, float eps, const void* W, int64_t ldw, int N, int K, float* logits, float* part_val, int* part_idx,
                              void* stream);
+/* FP8 decode weights (csrc/decode_w8.hip, csrc/decode_chain.hip; generate(decode_weights="fp8")).  afk_quantize_rows_fp8: W bf16 [N][ldw] -> Q uint8 [N][ldq], OCP e4m3fn
+ * codes (max finite 448, no infinities; not fnuz), and scale fp32 [N], one power of two per row: with a = max |w| of the row = m * 2^x, m in [0.5, 1), scale = 2^e where
+ * e = x - 9 for m <= 0.875 and x - 8 otherwise - the smallest power of two with a / 2^e <= 448 - never below 2^-117, and 1 for a row of zeros; code = RNE(w / 2^e).
+ * code * scale is exactly representable in bf16.  *bad (device int32, zeroed by the caller) is set to 1 when a weight is NaN or infinite.  One launch, one block per row.
+ * The four _w8 launches are the single-sequence launches above with W, ldw replaced by Wq, ldq, wscale: row r of the Linear is wscale[r] * code[r][:] (any positive fp32
+ * scale).  Dot products in fp32 over the widened codes (v_cvt_pk_f32_fp8), sum * wscale[r] in fp32, and from there the rounding points of the bf16 twin: bf16(sum + bias)
+ * -> RoPE's three roundings -> cache (qkv); bf16(sum) + residual -> bf16 (linear_residual); bf16(gate), bf16(up), bf16(silu) * up -> bf16 (gate_up); float(bf16(sum)) and
+ * the per-eight (max, argmax) of those values (lm_head).  K % 16 == 0, ldq % 16 == 0, Wq 16-byte aligned, otherwise the twin's conditions; AFK_CHAIN_S / AFK_CHAIN_R apply. */
+int afk_quantize_rows_fp8(const void* W, int64_t ldw, int N, int K, void* Q, int64_t ldq, float* scale, int* bad, void* stream);
+int afk_decode_chain_qkv_w8(const void* x, const void* norm_w, float eps, const void* Wq, int64_t ldq, const float* wscale, int K, const void* bias,
+                            const void* cos_t, const void* sin_t, const int* pos, void* q_out, void* kcache, void* vtcache, int spad, const int* start_dev,
+                            int Hq, int Hkv, int D, void* stream);
+int afk_decode_chain_linear_residual_w8(const void* x, const void* Wq, int64_t ldq, const float* wscale, int N, int K, const void* residual, void* out, void* stream);
+int afk_decode_chain_gate_up_w8(const void* x, const void* norm_w, float eps, const void* Wq, int64_t ldq, const float* wscale, int I, int K, void* act_out,
+                                void* stream);
+int afk_decode_chain_lm_head_w8(const void* x, const void* norm_w, float eps, const void* Wq, int64_t ldq, const float* wscale, int N, int K, float* logits,
+                                float* part_val, int* part_idx, void* stream);
 /* second stage + the bookkeeping between two decode steps of one sequence, one launch: token = argmax over the nparts pairs (ties: lowest row);
  * next_token[0] = token; tokens_out[state[2] + tok_off] = token (tokens_out may be null); state = int32 [key-range start, key-range end, cache slot, position]:
  * the last three += 1; x_out[H] = emb[token][:H] (the embedding lookup of the next step, Qwen2Model.embed_tokens). */
