@@ -23,7 +23,7 @@ class CfgSpec(NamedTuple):
 
 
 def resolve(guidance_scale=None, negative_prompt_ids=None, negative_prompt_attention_mask=None, generation_config=None, *, batch_size, audio_token_id=None,
-            num_beams=1, use_cache=True, exact_fp32=False, lookup=False, past=False, share_prompt=None):
+            num_beams=1, use_cache=True, exact_fp32=False, lookup=False, past=False, share_prompt=None, assist=False):
     """guidance_scale (keyword; None: the generation config's, by the rule generate() picks its other arguments with) -> CfgSpec, or None where guidance is
     inactive: no scale, or a scale of 1 (the reference's gate, utils.py:1132) - negative_prompt_* are then ignored, silently, as the reference ignores them.
     Any other float is taken (0, below 1, negative: the reference builds the processor for them).
@@ -31,8 +31,8 @@ def resolve(guidance_scale=None, negative_prompt_ids=None, negative_prompt_atten
     broadcast); a mask whose shape differs from the ids'.
     AfkError: a mask that is not LEFT padding; a negative prompt that holds the audio placeholder id (the unconditional branch has no audio: the reference
     calls model(input_ids, attention_mask) only); and the combinations guidance does not run with, each named: num_beams > 1, use_cache=False,
-    AFK_EXACT_FP32=1, prompt-lookup decoding (lookup), past_key_values= (past: the unconditional cache of the previous turn is not carried),
-    share_prompt=True (None takes the unshared route)."""
+    AFK_EXACT_FP32=1, prompt-lookup decoding (lookup), assisted decoding (assist: assistant_model=), past_key_values= (past: the unconditional cache of
+    the previous turn is not carried), share_prompt=True (None takes the unshared route)."""
     import torch
 
     from ._lib import AfkError
@@ -48,7 +48,8 @@ def resolve(guidance_scale=None, negative_prompt_ids=None, negative_prompt_atten
     if scale == 1.0:
         return None
     bad = [what for on, what in ((int(num_beams) > 1, "num_beams > 1"), (not use_cache, "use_cache=False"), (bool(exact_fp32), "AFK_EXACT_FP32=1"),
-                                 (bool(lookup), "prompt_lookup_num_tokens="), (bool(past), "past_key_values="), (share_prompt is True, "share_prompt=True")) if on]
+                                 (bool(lookup), "prompt_lookup_num_tokens="), (bool(assist), "assistant_model="), (bool(past), "past_key_values="),
+                                 (share_prompt is True, "share_prompt=True")) if on]
     if bad:
         raise AfkError(f"generate(guidance_scale={guidance_scale!r}) with {' / '.join(bad)}: classifier-free guidance runs with greedy or sampled decoding on a "
                        f"fresh KV cache of its own only (the unconditional rows are prefilled by this call)")

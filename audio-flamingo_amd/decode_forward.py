@@ -383,7 +383,7 @@ class AfkDecodeForwardMixin:
         self.last_w8_stats = _w8mod.stats(self._w8, rebuilt)
         return self._w8
 
-    def _w8_resolve(self, decode_weights, rows, num_beams, copies, guidance, lookup, share_prompt, use_cache, exact_fp32):
+    def _w8_resolve(self, decode_weights, rows, num_beams, copies, guidance, lookup, share_prompt, use_cache, exact_fp32, assist=False):
         """decode_w8.resolve with what only the model knows: the geometry"""
         on = (self.decode_weight_dtype if decode_weights is None else decode_weights) == "fp8"
         chain_ok = widths_ok = head_ok = True
@@ -392,7 +392,7 @@ class AfkDecodeForwardMixin:
             widths_ok = self.H % 16 == 0 and (self.Hq * self.D) % 16 == 0 and self.I % 16 == 0
             head_ok = self.arena["lm_head.weight"].data.shape[0] % 8 == 0
         return _w8mod.resolve(decode_weights, self.decode_weight_dtype, rows=rows, num_beams=num_beams, copies=copies, guidance=guidance, lookup=lookup,
-                              share_prompt=share_prompt, use_cache=use_cache, exact_fp32=exact_fp32, chain_ok=chain_ok, widths_ok=widths_ok, head_ok=head_ok)
+                              share_prompt=share_prompt, use_cache=use_cache, exact_fp32=exact_fp32, chain_ok=chain_ok, widths_ok=widths_ok, head_ok=head_ok, assist=assist)
 
     def _chain_layers(self, x, cache, pos_rows, krange, start_dev, aws=None, w8=None):
         """one new position of ONE sequence: five launches per decoder layer (round 4; ten on the split-K + glue path above).  Every Linear is one

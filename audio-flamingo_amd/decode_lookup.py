@@ -11,7 +11,8 @@ csrc/decode_lookup.hip; the contract is in include/afk.h), so the whole step sta
   draft_host / accept_host   the same two rules in torch ops with host reads (generate()'s lookup_on_device = False route)
 
 Deliberately not covered: sampled lookup (the draw for token t on row j needs the counter (t + j, 0); the sampler keys its counter by row), logits processors
-on candidate rows, assistant_model, batches."""
+on candidate rows, batches.  A draft model as the candidate source - generate(assistant_model=) - is decode_assist.py: it reuses build_state, accept and the
+verify forward of this route and replaces draft() by the draft model's own steps."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -34,7 +35,7 @@ def resolve(prompt_lookup_num_tokens=None, max_matching_ngram_size=None, generat
     (utils.py:1030).  ValueError where the reference raises one, with its message: a value <= 0, a batch of more than one sequence.  AfkError, naming the
     combination, for what this implementation does not run with lookup decoding: do_sample, num_beams > 1, use_cache=False, AFK_EXACT_FP32=1, logits processors
     (built-in or logits_processor=), the per-step hooks (stopping_criteria= / streamer=), stop strings, the output object - and k / ngram beyond the launches'
-    caps.  (assistant_model= is refused by generate() itself, with or without these keywords.)"""
+    caps.  (assistant_model= together with these keywords is refused by decode_assist.resolve.)"""
     from ._lib import AfkError
 
     gc = generation_config

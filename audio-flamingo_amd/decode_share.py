@@ -20,13 +20,13 @@ class ShareSpec(NamedTuple):
 
 
 def resolve(share_prompt=None, default=False, *, copies=1, num_beams=1, use_cache=True, exact_fp32=False, past=False, hooks=False, lookup=False,
-            beam_device=True, geometry=True):
+            beam_device=True, geometry=True, assist=False):
     """share_prompt (None: `default`, the model's share_prompt_cache) -> ShareSpec, or None for today's route: the switch off, or nothing to share
     (one continuation per prompt row).  copies: num_return_sequences of a sampled call; num_beams > 1: the beams are the continuations.
     The combinations sharing does not run with - share_prompt=True: an AfkError naming them; None with the default on: None, silently:
       use_cache=False; AFK_EXACT_FP32=1 (exact_fp32); past_key_values= (past); logits_processor= / stopping_criteria= / streamer= (hooks); prompt-lookup
-      decoding (lookup); beams on the host loop (beam_device False: beam_on_device off or outside afk_beam_step's caps); a geometry or row count outside the
-      batched decode chain or afk_attn_decode_shared's envelope (geometry False).
+      decoding (lookup); assisted decoding (assist: assistant_model=); beams on the host loop (beam_device False: beam_on_device off or outside
+      afk_beam_step's caps); a geometry or row count outside the batched decode chain or afk_attn_decode_shared's envelope (geometry False).
     Through generate() two of these never fire today, because an older refusal comes first and names the combination itself: a passed cache refuses
     num_return_sequences > 1 and num_beams > 1 ("generate(past_key_values=...) with ..."), and decode_lookup.resolve refuses do_sample and beams
     ("generate(prompt_lookup_num_tokens=...) with ..."), so no call with something to share reaches this function with past or lookup set.  They are kept so
@@ -43,6 +43,7 @@ def resolve(share_prompt=None, default=False, *, copies=1, num_beams=1, use_cach
         return None
     bad = [what for on, what in ((not use_cache, "use_cache=False"), (bool(exact_fp32), "AFK_EXACT_FP32=1"), (bool(past), "past_key_values="),
                                  (bool(hooks), "logits_processor= / stopping_criteria= / streamer="), (bool(lookup), "prompt_lookup_num_tokens="),
+                                 (bool(assist), "assistant_model="),
                                  (beams and not beam_device, "the host beam loop (beam_on_device off or outside afk_beam_step's caps)"),
                                  (not geometry, "a geometry or row count outside the batched decode chain or afk_attn_decode_shared's envelope")) if on]
     if bad:

@@ -21,13 +21,14 @@ LAYER_KEYS = ("self_attn.qkv.weight", "self_attn.o_proj.weight", "mlp.gate_up.we
 
 
 def resolve(decode_weights=None, default="bf16", *, rows=1, num_beams=1, copies=1, guidance=False, lookup=False, share_prompt=None, use_cache=True,
-            exact_fp32=False, chain_ok=True, widths_ok=True, head_ok=True):
+            exact_fp32=False, chain_ok=True, widths_ok=True, head_ok=True, assist=False):
     """decode_weights (None: `default`, the model's decode_weight_dtype) -> True where the call decodes on the FP8 copy, False for today's route ("bf16").
     Anything but None, "bf16" or "fp8" (keyword or default) is a ValueError.  FP8 runs on the single-sequence chain only; the calls that do not run it -
     decode_weights="fp8": an AfkError naming the combination; None with the default on: False, silently (the share_prompt convention):
       more than one row after input expansion (rows); num_beams > 1; num_return_sequences > 1 (copies); active guidance_scale (guidance); prompt-lookup
-      decoding (lookup); share_prompt=True; use_cache=False; AFK_EXACT_FP32=1 (exact_fp32); a geometry outside the single-sequence chain (chain_ok False);
-      hidden size, Hq * head_dim or intermediate size not a multiple of 16 (widths_ok False); lm_head rows not a multiple of 8 (head_ok False)."""
+      decoding (lookup); assisted decoding (assist: assistant_model=); share_prompt=True; use_cache=False; AFK_EXACT_FP32=1 (exact_fp32); a geometry
+      outside the single-sequence chain (chain_ok False); hidden size, Hq * head_dim or intermediate size not a multiple of 16 (widths_ok False); lm_head
+      rows not a multiple of 8 (head_ok False)."""
     from ._lib import AfkError
 
     for what, v in (("decode_weights", decode_weights), ("decode_weight_dtype", default)):
@@ -36,8 +37,8 @@ def resolve(decode_weights=None, default="bf16", *, rows=1, num_beams=1, copies=
     if (default if decode_weights is None else decode_weights) != "fp8":
         return False
     bad = [what for on, what in ((int(rows) > 1, "more than one row"), (int(num_beams) > 1, "num_beams > 1"), (int(copies) > 1, "num_return_sequences > 1"),
-                                 (bool(guidance), "guidance_scale="), (bool(lookup), "prompt_lookup_num_tokens="), (share_prompt is True, "share_prompt=True"),
-                                 (not use_cache, "use_cache=False"), (bool(exact_fp32), "AFK_EXACT_FP32=1"),
+                                 (bool(guidance), "guidance_scale="), (bool(lookup), "prompt_lookup_num_tokens="), (bool(assist), "assistant_model="),
+                                 (share_prompt is True, "share_prompt=True"), (not use_cache, "use_cache=False"), (bool(exact_fp32), "AFK_EXACT_FP32=1"),
                                  (not chain_ok, "a geometry outside the single-sequence decode chain"),
                                  (not widths_ok, "a hidden size, Hq * head_dim or intermediate size that is not a multiple of 16"),
                                  (not head_ok, "lm_head rows that are not a multiple of 8")) if on]

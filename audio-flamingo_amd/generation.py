@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib, ops
+from . import decode_assist as _assist
 from . import decode_cfg as _cfg
 from . import decode_lookup as _lookup
 from . import decode_process as _process
@@ -117,6 +118,8 @@ def continuation_mask_check(attention_mask, lo, P, S_total, who="generate(past_k
 class AfkGenerationMixin:
     beam_on_device = os.environ.get("AFK_BEAM_DEVICE", "1") == "1"   # beam search: the step's decisions and the cache move as launches of the decode step (csrc/decode_beam.hip)
     lookup_on_device = os.environ.get("AFK_LOOKUP_DEVICE", "1") == "1"   # prompt-lookup decoding: the draft and accept rules as launches of the step (csrc/decode_lookup.hip); off: torch ops and host reads
+    assist_on_device = os.environ.get("AFK_ASSIST_DEVICE", "1") == "1"   # assisted decoding: the draft model's steps and the two rules around them as launches of one step (csrc/decode_assist.hip); off: torch ops and host reads
+    last_assist_stats = None   # the last generate() call with an assistant_model: {emitted, steps, accepted, rejecting, launched, drafted}; None after every other call
     share_prompt_cache = os.environ.get("AFK_SHARE_PROMPT", "0") == "1"   # generate(share_prompt=None): sampled copies and device beams share the prompt's keys (decode_share.py, csrc/attention_shared.hip)
     last_share_stats = None   # the last generate() call that shared a prompt cache: decode_share.stats; None after every other call
     last_cfg_stats = None   # the last generate() call under classifier-free guidance: decode_cfg.stats; None after every other call
@@ -371,7 +374,8 @@ class AfkGenerationMixin:
                  no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, begin_suppress_tokens=None, min_p=None, typical_p=1.0,
                  epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, sequence_bias=None, bad_words_ids=None, min_length=0,
                  forced_eos_token_id=None, exponential_decay_length_penalty=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, share_prompt=None,
-                 guidance_scale=None, negative_prompt_ids=None, negative_prompt_attention_mask=None, decode_weights=None, **kwargs):
+                 guidance_scale=None, negative_prompt_ids=None, negative_prompt_attention_mask=None, decode_weights=None, assistant_model=None,
+                 num_assistant_tokens=None, **kwargs):
         """Greedy decoding, sampling or beam search on a KV cache, with GenerationMixin.generate's arguments and results; docs/generate.md describes every
         route, what it launches and how it differs from the reference.
 
@@ -412,13 +416,23 @@ class AfkGenerationMixin:
         an FP8 copy of the decoder Linears and the lm_head (OCP e4m3fn codes, one power-of-two scale per output row: half the bytes; decode_w8.py), built on
         first use and rebuilt when the weights have changed.  Weights only: the prefill, the activations and the cache are what they are, and the decode logits
         differ from the bf16 route by the quantisation.  "bf16": not one launch or allocation differs.  docs/generate.md, "FP8 decode weights".
+        assistant_model (None) with num_assistant_tokens (k; None: the assistant's generation_config.num_assistant_tokens, else 5): assisted (speculative)
+        decoding - a second, smaller model of this package with the same vocabulary drafts k tokens per step on a cache of its own (prefilled with the same
+        prompt and audio), this model verifies them in one pass over its weights and emits the confirmed ones plus one; the ids are the plain greedy ids.  The
+        whole step - the k draft steps included - is launches only (afk_assist_begin / afk_assist_stage around the single-sequence chain, then the verify
+        forward and afk_lookup_accept) and is captured like every other route; the class attribute assist_on_device (env AFK_ASSIST_DEVICE, default on) off,
+        or a draft geometry outside the single-sequence chain: the same rules as torch ops with host reads, eagerly.  Greedy, one sequence, a fresh bf16 KV
+        cache; every step drafts exactly k tokens (num_assistant_tokens_schedule "constant") and assistant_confidence_threshold is ignored.  None: not one
+        launch or allocation differs.  last_assist_stats; docs/generate.md, "Assisted decoding".
         generation_config (default: self.generation_config if there is one) supplies every argument left at its default.
 
         Returns the ids [B * num_return_sequences, S0 + n]: the prompt, then the new tokens, pad_token_id behind a row's end.
 
         Raises ValueError where the reference's validation does (max_new_tokens <= 0, num_return_sequences, min_p / typical_p, eos / pad / stop_strings
         forms, stop strings without a tokenizer, prompt-lookup values <= 0 or a batch) and AfkError for what is not built: prompt-lookup decoding with anything
-        but plain greedy decoding of one sequence (decode_lookup.resolve); unknown keywords, synced_gpus / use_model_defaults / assistant_model;
+        but plain greedy decoding of one sequence (decode_lookup.resolve); an assistant_model of another class, device or vocabulary, with more than 31 drafted
+        tokens, or with anything but plain greedy decoding of one sequence on a fresh bf16 cache (decode_assist.resolve; num_assistant_tokens <= 0 or no integer
+        and a batch: ValueError); unknown keywords, synced_gpus / use_model_defaults;
         attention masks that are not left padding; beams with do_sample or use_cache=False; the logits processors, hooks, stop strings or the output
         object with beams or with use_cache=False; stop strings or the output object with AFK_EXACT_FP32=1; tokenizer= without a stop string;
         output_attentions / output_hidden_states; past_key_values with num_beams > 1, use_cache=False, AFK_EXACT_FP32=1 or num_return_sequences > 1, with an
@@ -430,12 +444,12 @@ class AfkGenerationMixin:
         row, num_beams > 1, num_return_sequences > 1, guidance_scale, prompt-lookup decoding, share_prompt=True, use_cache=False, AFK_EXACT_FP32=1 or a
         geometry the single-sequence chain or its FP8 launches do not take (AfkError), any other value (ValueError) (decode_w8.resolve)."""
         self._require_hip()
-        self.last_share_stats = self.last_cfg_stats = self.last_w8_stats = None
+        self.last_share_stats = self.last_cfg_stats = self.last_w8_stats = self.last_assist_stats = None
         procs, criteria, streamer = kwargs.pop("logits_processor", None), kwargs.pop("stopping_criteria", None), kwargs.pop("streamer", None)
         out_kw = {k: kwargs.pop(k, None) for k in ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")}
         stop_strings, tokenizer = kwargs.pop("stop_strings", None), kwargs.pop("tokenizer", None) or None
         past = kwargs.pop("past_key_values", None)   # None: a fresh prefill, and not one launch or allocation differs
-        for k in ("synced_gpus", "use_model_defaults", "assistant_model"):
+        for k in ("synced_gpus", "use_model_defaults"):
             if kwargs.get(k):
                 raise AfkError(f"generate({k}=...) is not supported by this implementation")
             kwargs.pop(k, None)
@@ -475,18 +489,27 @@ class AfkGenerationMixin:
         cfg = _cfg.resolve(guidance_scale, negative_prompt_ids, negative_prompt_attention_mask, gc, batch_size=input_ids.shape[0],
                            audio_token_id=getattr(self, "audio_token_id", None), num_beams=int(num_beams), use_cache=bool(use_cache), exact_fp32=_exact.ENABLED,
                            lookup=prompt_lookup_num_tokens is not None or getattr(gc, "prompt_lookup_num_tokens", None) is not None, past=past is not None,
-                           share_prompt=share_prompt)
+                           share_prompt=share_prompt, assist=assistant_model is not None)
         if cfg is not None and share_prompt is None:
             share_prompt = False   # the class attribute on: a guided call takes the unshared route, silently
         # prompt-lookup decoding: keyword, else generation config; None: off, and nothing below changes
         lookup = _lookup.resolve(prompt_lookup_num_tokens, max_matching_ngram_size, gc, batch_size=input_ids.shape[0], do_sample=bool(do_sample), num_beams=int(num_beams),
                                  use_cache=bool(use_cache), exact_fp32=_exact.ENABLED, processors=spec.active or bool(procs), hooks=bool(criteria) or streamer is not None,
                                  stop_strings=bool(stop_spec.stop_strings), output_object=flags.return_dict)
+        # assisted decoding: the keyword; None: off, and nothing below changes
+        assist = None
+        if assistant_model is not None:
+            assist = self._assist_resolve(assistant_model, num_assistant_tokens, batch_size=input_ids.shape[0], do_sample=bool(do_sample), num_beams=int(num_beams),
+                                          copies=n_ret, use_cache=bool(use_cache), exact_fp32=_exact.ENABLED, processors=spec.active or bool(procs),
+                                          hooks=bool(criteria) or streamer is not None, stop_strings=bool(stop_spec.stop_strings), output_object=flags.return_dict,
+                                          past=past is not None, share_prompt=share_prompt, guidance=cfg is not None, decode_weights=decode_weights,
+                                          lookup=lookup is not None, prompt_len=input_ids.shape[1], max_new_tokens=max_new_tokens)
         # the shared prompt cache: keyword, else the class attribute; None: off or nothing to share, and nothing below changes
-        share = self._share_resolve(share_prompt, input_ids.shape[0], n_ret, int(num_beams), bool(use_cache), _exact.ENABLED, past is not None, hooks, lookup is not None, len(eos))
+        share = self._share_resolve(share_prompt, input_ids.shape[0], n_ret, int(num_beams), bool(use_cache), _exact.ENABLED, past is not None, hooks, lookup is not None, len(eos),
+                                    assist=assist is not None)
         # FP8 decode weights: keyword, else the class attribute; False: today's route, and nothing below changes
         fp8 = self._w8_resolve(decode_weights, input_ids.shape[0] * (n_ret if int(num_beams) == 1 else 1), int(num_beams), n_ret, cfg is not None, lookup is not None,
-                               share_prompt, bool(use_cache), _exact.ENABLED)
+                               share_prompt, bool(use_cache), _exact.ENABLED, assist=assist is not None)
         if spec.active and (num_beams > 1 or not use_cache):
             raise AfkError("generate(repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens / sequence_bias / "
                            "bad_words_ids / min_length / forced_eos_token_id / exponential_decay_length_penalty): greedy or sampled decoding on the KV cache "
@@ -517,7 +540,7 @@ class AfkGenerationMixin:
         dev = self.device_
         max_new = int(max_new_tokens)
         # a lookup step writes the cache slots of all its k + 1 rows; only the accepted ones ever become visible, so the cache needs k more positions
-        headroom = max_new_tokens + (lookup.k if lookup else 0)
+        headroom = max_new_tokens + (lookup.k if lookup else 0) + (assist.k if assist else 0)   # (an assisted step: the same k + 1 rows)
         if share is not None or cfg is not None:   # the prompt rows run once, into a cache that only ever holds the prompt: the generated positions go to the tail
             headroom = 0                           # cache (sharing) or to the combined cache of both branches (guidance)
         cont = self._continue_from(past, attention_mask, B, S0, headroom) if past is not None else None   # (the caller's object, its AfkKVCache form, P)
@@ -555,6 +578,8 @@ class AfkGenerationMixin:
             guide, (Kc, Vt), lo, uncond_first = self._cfg_setup(cfg, ids, (Kc, Vt), lo, S0, max_new, V)
         if lookup is not None:
             return self._continue_done(cont, self._generate_lookup(ids, first_logits, (Kc, Vt), lo, lookup, max_new, eos, use_graph))
+        if assist is not None:
+            return self._generate_assisted(ids, input_features, input_features_mask, attention_mask, first_logits, (Kc, Vt), lo, assist, max_new, eos, use_graph)
         rec = None
         if flags.collect:   # one [max_new_tokens, B, V] fp32 buffer per kind, allocated once: static memory the captured step writes a slot of
             new_buf = lambda: torch.empty((max_new, B, V), device=dev, dtype=torch.float32)
@@ -617,7 +642,7 @@ class AfkGenerationMixin:
                 new = torch.where(after, torch.full_like(new, pad), new)
         return self._continue_done(cont, self._generate_output(flags, torch.cat([ids, new], dim=1), S0, rec, st.cache, lo, shared=shared, cfg=guide))
 
-    def _share_resolve(self, share_prompt, B0, copies, num_beams, use_cache, exact_fp32, past, hooks, lookup, n_eos):
+    def _share_resolve(self, share_prompt, B0, copies, num_beams, use_cache, exact_fp32, past, hooks, lookup, n_eos, assist=False):
         """decode_share.resolve with what only the model knows: whether the device beam step takes the call, whether B0 * n rows take the batched decode chain
         and the geometry lies inside afk_attn_decode_shared's envelope"""
         n = num_beams if num_beams > 1 else copies
@@ -627,7 +652,17 @@ class AfkGenerationMixin:
             geometry = ops.attn_shared_supported(self.Hq, self.Hkv, self.D, n) and self._chain_batched_ok(B0 * n, self.arena["lm_head.weight"].data)
             beam_device = self.beam_on_device and ops.beam_caps_ok(num_beams, n_eos, self.V)
         return _share.resolve(share_prompt, self.share_prompt_cache, copies=copies, num_beams=num_beams, use_cache=use_cache, exact_fp32=exact_fp32, past=past,
-                              hooks=hooks, lookup=lookup, beam_device=beam_device, geometry=geometry)
+                              hooks=hooks, lookup=lookup, beam_device=beam_device, geometry=geometry, assist=assist)
+
+    def _assist_resolve(self, assistant_model, num_assistant_tokens, **flags):
+        """decode_assist.resolve with what only the two models know: the assistant's class and device, both vocabularies, both position limits"""
+        from .modeling import AudioFlamingo3ForConditionalGeneration
+
+        is_model = isinstance(assistant_model, AudioFlamingo3ForConditionalGeneration)   # Music Flamingo's class derives from it
+        vocab = lambda m: (m.arena[m._lm + "embed_tokens.weight"].data.shape[0], m.arena["lm_head.weight"].data.shape[0], m.audio_token_id)
+        limits = (int(self.config.text_config.max_position_embeddings), int(assistant_model.config.text_config.max_position_embeddings)) if is_model else None
+        return _assist.resolve(assistant_model, num_assistant_tokens, is_model=is_model, same_device=not is_model or assistant_model.arena["lm_head.weight"].data.device == self.arena["lm_head.weight"].data.device,
+                               target_vocab=vocab(self) if is_model else None, assistant_vocab=vocab(assistant_model) if is_model else None, max_positions=limits, **flags)
 
     def _cfg_setup(self, cfg, ids, cond_cache, lo, S0, max_new, V):
         """the unconditional branch of a guided call behind the main prefill (UnbatchedClassifierFreeGuidanceLogitsProcessor.get_unconditional_logits'
@@ -714,6 +749,75 @@ class AfkGenerationMixin:
         st = ls["status"].tolist()
         self.last_lookup_stats = dict(emitted=st[_lookup.EMITTED], steps=st[_lookup.STEPS], accepted=st[_lookup.ACCEPTED], rejecting=st[_lookup.REJECTING],
                                       launched=launched)
+        return torch.cat([ids, ls["tokens"][None, :st[_lookup.EMITTED]]], dim=1)
+
+    @torch.no_grad()
+    def _generate_assisted(self, ids, input_features, input_features_mask, attention_mask, first_logits, cache, lo, assist, max_new, eos, use_graph):
+        """greedy decoding of one sequence with a draft model (decode_assist.py): the assistant is prefilled on the same ids, audio and mask through its own
+        audio tower into a cache of its own (k + 1 positions of headroom), so slots and positions agree between the two models; token 0 is the argmax of the
+        target's prefill logits; from then on a step is
+          afk_assist_begin (the assistant's step state <- the target's, its input row <- its embedding of the last emitted token)
+          -> k single-sequence steps of the assistant (_chain_layers -> _chain_lm_head, partial argmaxes only -> afk_decode_select_greedy: draft token j, its
+             input's keys at slot cur + j) -> ONE more _chain_layers pass on the last draft (its keys at slot cur + k: when all k drafts are accepted the next
+             step starts behind it, and without it the assistant would attend to a hole there - the ids would stay right and the acceptance rate drop)
+          -> afk_assist_stage (the drafts as candidates, cut behind an eos id and to the budget + the target's k + 1 input rows)
+          -> _lookup_forward (one pass over the target's weights) -> afk_lookup_accept (the confirmed prefix + one token; [end, cur, position] advanced).
+        The next step's begin copies the advanced state, which rewinds the assistant past rejected drafts; their slots are overwritten.  Nothing depends on
+        the host, so _run_steps captures and replays the step; the host polls the status words every 8th step (behind `done` a step rewrites the same assistant
+        slots, stages no candidate and accepts nothing).  assist_on_device = False, or an assistant outside the single-sequence chain: the same rules in torch
+        ops with host reads around the same verify forward, eagerly.  self.last_assist_stats: {emitted, steps, accepted, rejecting} of the call, `launched`
+        (the steps enqueued: up to seven more than `steps` on the device route) and `drafted` (k per step that was open)."""
+        dev, S0, k, am = self.device_, ids.shape[1], assist.k, assist.model
+        M = k + 1
+        am._require_hip()
+        lo_a, padded, Ka, Va, pos_rows, krange, fast = am._prefill_setup(attention_mask, 1, S0, max_new + k + 1, "generate(assistant_model=...)")
+        am._decode_layers(am._merged_embeddings(ids, input_features, input_features_mask), 1, S0, 0, (Ka, Va), pos_rows, krange, fast, kv_lo=lo_a if padded else None)
+        head, emb = self.arena["lm_head.weight"].data, self.arena[self._lm + "embed_tokens.weight"].data
+        state = torch.cat([lo, torch.tensor([S0 + 1, S0], device=dev, dtype=torch.int32), S0 - lo]).contiguous()   # [lo, key-range end, cache slot, position]
+        ls = _lookup.build_state(_lookup.LookupSpec(k, 1), ids, self._select_token(first_logits), max_new, eos, state, emb.shape[1])
+        aws = self._decode_attn_workspace(dev, cache[1].shape[4], M) if self._lookup_chain_ok(M, head) else None
+        a = _assist.build_state(am, k, (Ka, Va), dev)
+        on_device = self.assist_on_device and a.aws is not None
+        verify = lambda: self._lookup_forward(ls["x"], cache, ls["pos"], ls["krange"], state[2:3], aws, head)
+
+        def step():
+            _assist.begin(ls, a)
+            for j in range(M):
+                x = am._chain_layers(a.x0, a.cache, a.dstate[3:4], a.dstate[0:2], a.dstate[2:3], aws=a.aws)
+                if j == k:   # the last draft's keys only: no lm_head, no selection
+                    break
+                am._chain_lm_head(x, a.head, part_val=a.part_val, part_idx=a.part_idx)
+                _lib.call("afk_decode_select_greedy", a.part_val.data_ptr(), a.part_idx.data_ptr(), a.part_val.numel(), a.nxt.data_ptr(), a.draft.data_ptr(), 0,
+                          a.dstate.data_ptr(), a.emb.data_ptr(), a.emb.stride(0), a.emb.shape[1], a.x0.data_ptr(), ops._stream())
+            _assist.stage(ls, a, emb)
+            _lookup.accept(ls, verify())
+
+        def host_step():
+            _assist.begin_host(ls, a)
+            cur = int(a.dstate[2])
+            for j in range(M):
+                logits = am._decode_logits(dst)   # appends the keys of a.nxt at slot dstate[2]
+                a.dstate[1:4] += 1
+                if j == k:
+                    break
+                a.nxt.copy_(self._select_token(logits))
+                a.draft[cur + j] = a.nxt[0]
+            _assist.stage_host(ls, a, emb)
+            _lookup.accept_host(ls, verify())
+
+        done = lambda t=0: ls["status"].tolist()[_lookup.DONE] != 0   # one small copy
+        launched = 0
+        if on_device:
+            launched = _run_steps(step, max_new, use_graph, done)
+        else:
+            dst = am._new_state(a.cache, lo_a, S0, a.nxt, aws=a.aws)
+            dst.cur, dst.single = a.dstate[2:3], SingleSequence(state=a.dstate, kr1=a.dstate[0:2], pos1=a.dstate[3:4], advance=a.dstate[1:4])
+            while not done():
+                host_step()
+                launched += 1
+        st = ls["status"].tolist()
+        self.last_assist_stats = dict(emitted=st[_lookup.EMITTED], steps=st[_lookup.STEPS], accepted=st[_lookup.ACCEPTED], rejecting=st[_lookup.REJECTING],
+                                      launched=launched, drafted=k * st[_lookup.STEPS])
         return torch.cat([ids, ls["tokens"][None, :st[_lookup.EMITTED]]], dim=1)
 
     @staticmethod

@@ -623,6 +623,32 @@ int afk_lookup_draft(const int* ids, int ids_cap, int* status, const int* state,
                      int64_t* rows, int* pos, int* krange, const void* emb, int64_t ld_emb, int vocab, int H, void* x_out, int64_t ldx, void* stream);
 int afk_lookup_accept(const float* logits, int64_t ld_logits, int V, int M, const int* cand, int* ids, int ids_cap, int64_t* tokens_out, int max_new,
                       int* status, int* state, const int* eos, int n_eos, int* sel, float* ws, void* stream);
+/* Assisted (speculative) decoding on the device (csrc/decode_assist.hip; generate(assistant_model=draft, num_assistant_tokens=k), greedy, one sequence): what
+ * GenerationMixin._assisted_decoding (transformers/generation/utils.py:3562-3830) does on the host around the draft model's steps with an
+ * AssistedCandidateGenerator (transformers/generation/candidate_generator.py), as launches.  A step is afk_assist_begin -> k single-sequence steps of the draft
+ * model on dstate (each ends in afk_decode_select_greedy with tokens_out = draft, tok_off = 0) -> one more pass of its layers -> afk_assist_stage -> the verify
+ * forward of the target on M = k + 1 rows -> afk_lookup_accept.  ids, status and state are the ones of afk_lookup_draft / afk_lookup_accept; both caches were
+ * prefilled with the same prompt, so cache slots and positions agree between the two models.  Both entries: one block, enqueue-only, no allocation, capturable,
+ * every position-dependent value read from device memory, no atomics and no counters.
+ *
+ * afk_assist_begin: dstate[0 .. 4) = state[0 .. 4) (the draft model's own running copy of {lo, key-range end, cache slot, position}: the k selections of the
+ *   step advance it, the next step's begin rewinds it to what the target accepted) and x_out[H] bf16 = emb[ids[len - 1]][:H], the DRAFT model's embedding row of the
+ *   last emitted token (len = status[0] clamped to [1, ids_cap], the id clamped to [0, vocab)).  status is only read: with done != 0 the launch rewrites the values of
+ *   the step before, which nothing reads.  H % 8 == 0, 16-byte rows (ld_emb a multiple of 8, >= H).
+ *
+ * afk_assist_stage = afk_lookup_draft's steps 2 and 3 with the candidates taken from the drafted tokens: draft [draft_cap] int64 holds drafted token j of this
+ *   step at draft[state[2] + j] (afk_decode_select_greedy wrote it at the cache slot its step appended at; the index is clamped to [0, draft_cap)).
+ *   1. n_cand = the number of leading drafts kept: k, cut BEHIND the first id in eos[n_eos] (the eos itself stays a candidate: the draft model would have stopped
+ *      there and the target may confirm it), and to max_new - emitted - 1 (emitted == max_new - 1: none).  done != 0: none.
+ *   2. out: status[3] = n_cand; cand [k] int32 (entries behind n_cand repeat ids[len - 1]); rows [M] int64 = {ids[len - 1], cand[0 .. k)}; pos [M] = state[3] + j;
+ *      krange [M][2] = {state[0], state[1] + j}; x_out [M][ldx] bf16 = emb[rows[j]][:H], the TARGET's embedding rows (ids clamped to [0, vocab)).
+ *   1 <= k <= AFK_LOOKUP_MAX_K, max_new >= 1; H % 8 == 0, 16-byte rows (ld_emb, ldx multiples of 8, >= H).  Nothing but status[3] and the outputs is written.
+ * Refused (both): a null pointer, k outside [1, AFK_LOOKUP_MAX_K], H % 8 != 0 or rows that are not 16-byte aligned, an eos count with a null list. */
+int afk_assist_begin(const int* ids, int ids_cap, const int* status, const int* state, int* dstate, const void* emb, int64_t ld_emb, int vocab, int H,
+                     void* x_out, void* stream);
+int afk_assist_stage(const int* ids, int ids_cap, int* status, const int* state, int k, int max_new, const int* eos, int n_eos, const int64_t* draft,
+                     int draft_cap, int* cand, int64_t* rows, int* pos, int* krange, const void* emb, int64_t ld_emb, int vocab, int H, void* x_out,
+                     int64_t ldx, void* stream);
 /* One step of beam search on the device (csrc/decode_beam.hip; generate(num_beams > 1)): what GenerationMixin._beam_search does between two forward passes
  * (transformers/generation/utils.py: _get_top_k_continuations, _update_finished_beams, _get_running_beams_for_next_iteration, _check_early_stop_heuristic,
  * _beam_search_has_unfinished_sequences), ONE call per generated token - two launches, a block per (row, beam) and a block per row - with no host state.
