@@ -346,3 +346,61 @@ class _LMHeadLoss(torch.autograd.Function):
 def lm_head_loss(x, w, shift_labels, rows=None):
     """mean CE of (x @ w^T) against shift_labels (-100 = ignore); rows = int64 indices of the labelled rows (None: all)"""
     return _LMHeadLoss.apply(x, w, shift_labels, rows)
+
+
+class _LMHeadLogprob(torch.autograd.Function):
+    """lm_head + per-row log-probability of the label, chunked (functional.LMHeadLogprobFn in tensor-returning form): the forward keeps the gathered
+    x, the labels and the log-sum-exp; the backward recomputes each logits chunk with the same GEMM, turns it into u * (onehot - softmax) in place and
+    feeds the dgrad / wgrad GEMMs"""
+
+    CHUNK = 4096
+
+    @staticmethod
+    def forward(ctx, x, w, shift_labels, rows, entropy):
+        M_all = x.shape[0]
+        xs = ops.gather_rows(x, rows) if rows is not None else x
+        labs = shift_labels.index_select(0, rows) if rows is not None else shift_labels
+        M, V = xs.shape[0], w.shape[0]
+        dev = x.device
+        logp = torch.empty(M, device=dev, dtype=torch.float32)
+        lse = torch.empty(M, device=dev, dtype=torch.float32)
+        ent = torch.empty(M, device=dev, dtype=torch.float32) if entropy else None
+        chunk = min(_LMHeadLogprob.CHUNK, M)
+        buf = torch.empty((chunk, V), device=dev, dtype=BF16)
+        for s in range(0, M, chunk):
+            e = min(M, s + chunk)
+            logits = buf[: e - s]
+            ops.gemm_nt(xs[s:e], w, out=logits)
+            ops.token_logprob(logits, labs[s:e], logp[s:e], lse[s:e], None if ent is None else ent[s:e])
+        # under no_grad nothing of this is kept (autograd drops what a Function saves when no input requires grad or grad mode is off)
+        ctx.save_for_backward(xs, w, labs, lse, rows)
+        ctx.M_all = M_all
+        if entropy:
+            ctx.mark_non_differentiable(ent)
+            return logp, ent
+        return logp
+
+    @staticmethod
+    def backward(ctx, u, *_):
+        xs, w, labs, lse, rows = ctx.saved_tensors
+        M, V = xs.shape[0], w.shape[0]
+        u = u.reshape(M).float().contiguous()
+        dxs = torch.empty_like(xs)
+        dw = torch.empty_like(w)
+        chunk = min(_LMHeadLogprob.CHUNK, M)
+        buf = torch.empty((chunk, V), device=xs.device, dtype=BF16)
+        for i, s in enumerate(range(0, M, chunk)):
+            e = min(M, s + chunk)
+            logits = buf[: e - s]
+            ops.gemm_nt(xs[s:e], w, out=logits)                                                   # the forward's logits, bit for bit
+            ops.token_logprob_bwd_(logits, labs[s:e], lse[s:e], u[s:e])
+            ops.gemm(logits, w, out=dxs[s:e], trans_b=True)                                       # dX = dlogits . W
+            ops.gemm(logits, xs[s:e], out=dw, trans_a=True, trans_b=True, accumulate=i > 0)       # dW += dlogits^T . X
+        dx = ops.scatter_rows(dxs, rows, ctx.M_all) if rows is not None else dxs
+        return dx, dw, None, None, None
+
+
+def lm_head_logprob(x, w, shift_labels, rows=None, entropy=False):
+    """log_softmax(x @ w^T, -1)[label] per row as fp32 [M] (0 on a row whose label is -100), differentiable in x and w with any per-row upstream
+    gradient; rows = int64 indices of the labelled rows (None: all; M = len(rows) then).  entropy=True: -> (logp, entropy [M]), the entropy detached"""
+    return _LMHeadLogprob.apply(x, w, shift_labels, rows, bool(entropy))

@@ -687,6 +687,104 @@ class LMHeadLossFn:
         return dx, None, None, None, None, None, None
 
 
+class LMHeadLogprobFn:
+    """lm_head + per-row log-probability of the label without materialising [B*S, V]: log_softmax(lm_head(x).float(), -1).gather(-1, labels), the quantity
+    preference optimisation, GRPO / PPO and weighted SFT differentiate with a gradient that differs per token.
+
+    The second loss-head stage beside LMHeadLossFn.  That one writes d loss / d logits during the forward sweep for an upstream gradient of 1; here the
+    upstream gradient d L / d logp may depend on the log-probabilities themselves and is not known before the forward has finished, so
+        forward   per CHUNK rows: lm_head GEMM into the reused chunk buffer -> afk_token_logprob (one sweep, nothing written to the chunk) -> logp, lse
+        backward  per CHUNK rows: the SAME GEMM on the same operands (bit-identical logits: the saved lse is theirs) -> afk_token_logprob_bwd turns
+                  the chunk into u * (onehot - softmax) in place -> the dgrad / wgrad GEMMs of LMHeadLossFn consume it; dW lands in the gradient arena.
+    The recompute costs one lm_head GEMM over the labelled rows; nothing vocabulary-sized is kept between forward and backward.  The stage returns
+    logp [M] fp32, or [2, M] = (logp, entropy) when the entropy is asked for (the entropy row is not differentiable: its gradient is ignored)."""
+
+    CHUNK = 4096  # as LMHeadLossFn
+
+    @staticmethod
+    def grad_keys(arena, wkey, entropy):
+        # announced at forward time (stage_ops): a weight gradient that LMHeadLossFn parked in the arena slice is moved out before this stage's
+        # backward writes there (Arena.expect_writes)
+        return [wkey]
+
+    @staticmethod
+    def _forms(blk, chunk, H):
+        direct = BWD_FORM == "direct"
+        wdirect = direct or BWD_FORM == "wgrad_direct"
+        nn_dgrad = LMHEAD_NN_DGRAD and not direct and H % 8 == 0 and _tiles256(chunk, H) < DIRECT_MIN_TILES   # see LMHeadLossFn.forward
+        return direct, wdirect, nn_dgrad
+
+    @staticmethod
+    def forward(ctx, x, anchor, arena, wkey, shift_labels, entropy=False, rows=None):
+        M_all = x.shape[0]
+        if rows is not None:   # the positions whose shifted label is not -100, as LMHeadLossFn gathers them
+            x = ops.gather_rows(x, rows)
+            shift_labels = shift_labels.index_select(0, rows)
+        M, H = x.shape
+        blk = arena[wkey]
+        V = blk.shape[0]
+        dev = x.device
+        need_grad = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        out = torch.empty((2, M) if entropy else (M,), device=dev, dtype=torch.float32)
+        logp, ent = (out[0], out[1]) if entropy else (out, None)
+        lse = torch.empty(M, device=dev, dtype=torch.float32)
+        chunk = min(LMHeadLogprobFn.CHUNK, M)
+        buf = torch.empty((chunk, V), device=dev, dtype=torch.bfloat16)
+        if need_grad and LMHeadLogprobFn._forms(blk, chunk, H)[2] and not blk.shadow_lazy:
+            blk.shadow_lazy = True   # the backward's dgrad reads W as stored: no W^T shadow of lm_head is refreshed per step for it
+        for s in range(0, M, chunk):
+            e = min(M, s + chunk)
+            logits = buf[: e - s]
+            ops.gemm_nt(x[s:e], blk.data, out=logits)
+            ops.token_logprob(logits, shift_labels[s:e], logp[s:e], lse[s:e], None if ent is None else ent[s:e])
+        if need_grad:
+            # the weights the saved lse belongs to: a host-side scalar, read in backward without a device sync
+            ctx.save_for_backward(x, shift_labels, lse, rows, torch.tensor([arena.version()], dtype=torch.int64))
+        ctx.meta = (arena, wkey, M_all, bool(entropy))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, shift_labels, lse, rows, weights_at = ctx.saved_tensors
+        arena, wkey, M_all, entropy = ctx.meta
+        if int(weights_at[0]) != arena.version():
+            raise ops.AfkError("lm_head_logprob: the parameters changed between this stage's forward and its backward (optimizer step / load_state_dict): "
+                               "the saved log-sum-exp belongs to the old weights and the recomputed logits would not; run backward before the step")
+        M, H = x.shape
+        blk = arena[wkey]
+        V = blk.shape[0]
+        u = (g[0] if entropy else g).reshape(M).float().contiguous()   # d L / d logp per row; the entropy row carries no gradient
+        dx = torch.empty_like(x)
+        chunk = min(LMHeadLogprobFn.CHUNK, M)
+        buf = torch.empty((chunk, V), device=x.device, dtype=torch.bfloat16)
+        direct, wdirect, nn_dgrad = LMHeadLogprobFn._forms(blk, chunk, H)
+        wt = arena.shadow(wkey) if not direct and not nn_dgrad else None
+        if not blk.fresh:
+            arena.join_streams()   # another head's weight gradient (LMHeadFn: linear_bwd on the wgrad stream) may still be landing in the slice
+        acc = not blk.fresh
+        for s in range(0, M, chunk):
+            e = min(M, s + chunk)
+            logits = buf[: e - s]
+            ops.gemm_nt(x[s:e], blk.data, out=logits)
+            ops.token_logprob_bwd_(logits, shift_labels[s:e], lse[s:e], u[s:e])
+            if direct or nn_dgrad:
+                ops.gemm(logits, blk.data, out=dx[s:e], trans_b=True)                               # dX = dlogits . W
+            else:
+                ops.gemm_nt(logits, wt, out=dx[s:e], K=V)
+            if wdirect:
+                ops.gemm(logits, x[s:e], out=blk.grad, trans_a=True, trans_b=True, accumulate=acc)  # dW += dlogits^T . X
+            else:
+                dlt = ops.transpose(logits)      # [V, pad64(n)]
+                xt = ops.transpose(x[s:e])       # [H, pad64(n)]
+                ops.gemm_nt(dlt, xt, out=blk.grad, accumulate=acc)
+                del dlt, xt
+            acc = True
+        arena.grad_written(blk)
+        if rows is not None:
+            dx = ops.scatter_rows(dx, rows, M_all)
+        return dx, None, None, None, None, None, None
+
+
 # ---------------------------------------------------------------------------------------------- the stages as registered operators
 # <Stage>Fn.apply(...) - what modeling.py calls - dispatches torch.ops.afk.<stage> (stage_ops.py): schema, fake implementation, backward operator
 # with the gradient arena declared as mutated, autograd registration.  Slot kinds per forward argument: T tensor, T? optional tensor, A arena, S static.
@@ -702,3 +800,4 @@ DecoderLayerFn.apply = staticmethod(register_stage("decoder_layer", DecoderLayer
 RMSNormFn.apply = staticmethod(register_stage("final_rms_norm", RMSNormFn, ("T", "T", "A", "S", "S")))
 LMHeadFn.apply = staticmethod(register_stage("lm_head", LMHeadFn, ("T", "T", "A", "S")))
 LMHeadLossFn.apply = staticmethod(register_stage("lm_head_loss", LMHeadLossFn, ("T", "T", "A", "S", "T", "T", "T?")))
+LMHeadLogprobFn.apply = staticmethod(register_stage("lm_head_logprob", LMHeadLogprobFn, ("T", "T", "A", "S", "T", "S", "T?")))

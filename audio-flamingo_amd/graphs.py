@@ -13,7 +13,8 @@ What changes between replays lives in device memory, never in kernel arguments:
       ``FusedAdamW.advance()`` right before each replay.
 Not capturable (use the eager step): data-dependent host decisions - ``check_placeholders`` (host sync), labels / masks whose
 valid-row count changes from step to step, gradient checkpointing via torch.utils.checkpoint, and (not validated on this pool's
-1-GPU boxes) RCCL collectives inside the capture - bench.py keeps the eager path for world > 1.
+1-GPU boxes) RCCL collectives inside the capture - bench.py keeps the eager path for world > 1.  A step with
+``forward(return_token_logprobs=True)`` is refused with an AfkError: the graph keeps the mean-CE loss route only.
 """
 from __future__ import annotations
 
@@ -41,9 +42,15 @@ class GraphedTrainStep:
         cur = torch.cuda.current_stream()
         s = stream if stream is not None else torch.cuda.Stream(device=model.device_)
         s.wait_stream(cur)
-        with torch.cuda.stream(s):
-            for _ in range(max(warmup, 1)):
-                step_body()
+        # the loss route only: forward(return_token_logprobs=True) raises while this is set, and during the capture itself (a user loss on
+        # out.token_logprobs, and the host-side check of its backward that the weights have not moved since the forward, are not part of a replayed step)
+        model._graphed_step = True
+        try:
+            with torch.cuda.stream(s):
+                for _ in range(max(warmup, 1)):
+                    step_body()
+        finally:
+            model._graphed_step = False
         cur.wait_stream(s)
         torch.cuda.synchronize()
         torch.cuda.empty_cache()  # hand the eager steps' cached activation blocks back: the graph brings its own pool

@@ -54,10 +54,13 @@ class AF3Output:
     final hidden states the output keeps): a training loop that only reads ``out.loss`` / ``out[0]`` never pays for it, ``Trainer.evaluate``
     / ``compute_metrics`` (which read ``outputs[1:]``) get what they expect."""
 
-    _FIELDS = ("loss", "logits", "past_key_values", "hidden_states", "attentions", "audio_hidden_states")
+    _FIELDS = ("loss", "logits", "past_key_values", "hidden_states", "attentions", "audio_hidden_states", "token_logprobs", "token_entropy")
 
-    def __init__(self, loss=None, logits=None, past_key_values=None, hidden_states=None, attentions=None, audio_hidden_states=None, logits_fn=None):
+    def __init__(self, loss=None, logits=None, past_key_values=None, hidden_states=None, attentions=None, audio_hidden_states=None, logits_fn=None,
+                 token_logprobs=None, token_entropy=None):
         self.loss, self._logits, self._logits_fn = loss, logits, logits_fn
+        # forward(labels=, return_token_logprobs=True): fp32 [B, S] aligned with labels (docs/token_logprobs.md); None when not asked for
+        self.token_logprobs, self.token_entropy = token_logprobs, token_entropy
         self.past_key_values, self.hidden_states, self.attentions, self.audio_hidden_states = past_key_values, hidden_states, attentions, audio_hidden_states
 
     @property
@@ -592,11 +595,26 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, AfkDecodeForwar
 
     def forward(self, input_ids=None, input_features=None, input_features_mask=None, attention_mask=None, position_ids=None,
                 past_key_values=None, inputs_embeds=None, labels=None, use_cache=None, logits_to_keep=0, return_logits=None,
-                num_items_in_batch=None, **kwargs):
+                num_items_in_batch=None, return_token_logprobs=False, return_token_entropy=False, **kwargs):
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
+        if return_token_logprobs and labels is None:
+            raise ValueError("return_token_logprobs=True needs labels: the log-probabilities are those of the label tokens")
+        if return_token_entropy and not return_token_logprobs:
+            raise ValueError("return_token_entropy=True needs return_token_logprobs=True: the entropy comes out of the same sweep over the logits")
         self._require_hip()
         from . import exact as _exact
+
+        if return_token_logprobs:
+            if past_key_values is not None or use_cache:
+                raise AfkError("forward(return_token_logprobs=True, use_cache=True / past_key_values=...): the KV-cache path is inference only and has no "
+                               "loss head; score the tokens with a plain labelled forward")
+            if self._graphed_step or torch.cuda.is_current_stream_capturing():
+                raise AfkError("forward(return_token_logprobs=True) inside GraphedTrainStep / a HIP-graph capture: the replayed step keeps the mean-CE "
+                               "loss route only; run the step with a loss on out.token_logprobs eagerly")
+            if _exact.ENABLED:
+                raise AfkError("forward(return_token_logprobs=True) under AFK_EXACT_FP32=1: the exact-fp32 verification forward has no loss head; "
+                               "unset AFK_EXACT_FP32")
 
         if _exact.ENABLED and labels is None and inputs_embeds is None and past_key_values is None and not torch.is_grad_enabled():
             # AFK_EXACT_FP32=1 (verification mode, exact.py): the inference forward in exact fp32 on the afk_x32_* kernels - fp32 logits, no KV cache.
@@ -699,7 +717,7 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, AfkDecodeForwar
         if want_hidden:
             hidden.append(x.reshape(B, S, -1))                            # ... with the LAST entry taken after the final norm (lm_head(hidden[-1]) == logits)
             hidden = tuple(hidden)
-        loss, logits = None, None
+        loss, logits, token_logprobs, token_entropy = None, None, None, None
         if labels is not None:
             if last_rows is not None:   # x already holds the labelled rows only, in order
                 shift, rows = shift.index_select(0, last_rows), None
@@ -707,7 +725,23 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, AfkDecodeForwar
                 denom = torch.as_tensor(num_items_in_batch, device=self.device_, dtype=torch.float32).reshape(1)
             else:
                 denom = ops.count_valid(shift)
-            loss = F_.LMHeadLossFn.apply(x, self._anchor("lm_head.weight"), a, "lm_head.weight", shift, denom, rows)
+            if return_token_logprobs:
+                # the per-token stage (F_.LMHeadLogprobFn): log p(label) per labelled row, with a gradient per row; the mean-CE stage does not run -
+                # out.loss is built from the same tensor by torch ops
+                at = last_rows if last_rows is not None else rows        # the flat positions (of the SHIFTED labels) x / rows stand for; None = every row
+                lp = F_.LMHeadLogprobFn.apply(x, self._anchor("lm_head.weight"), a, "lm_head.weight", shift, bool(return_token_entropy), rows)
+                lp, ent = (lp[0], lp[1].detach()) if return_token_entropy else (lp, None)
+
+                def _place(v):
+                    # row i = b * S + t - 1 of the shifted labels scores labels[b, t]: one step to the right; [b, 0] and every ignored position stay 0
+                    flat = v if at is None else torch.zeros(B * S, device=v.device, dtype=v.dtype).index_copy(0, at, v)
+                    return torch.nn.functional.pad(flat.reshape(B, S)[:, :-1], (1, 0))
+
+                token_logprobs = _place(lp)
+                token_entropy = None if ent is None else _place(ent)
+                loss = -(token_logprobs.sum() / denom.reshape(()).clamp_min(1.0))
+            else:
+                loss = F_.LMHeadLossFn.apply(x, self._anchor("lm_head.weight"), a, "lm_head.weight", shift, denom, rows)
             if self._rows_poison is not None:   # label_rows_static promise broken -> NaN loss (see _valid_rows); 0.0 otherwise
                 loss, self._rows_poison = loss + self._rows_poison, None
         def _logits(xh=x):
@@ -717,7 +751,8 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, AfkDecodeForwar
             return F_.LMHeadFn.apply(xs, self._anchor("lm_head.weight"), a, "lm_head.weight").reshape(B, -1, self.V)
 
         if labels is None or return_logits:
-            return AF3Output(loss=loss, logits=_logits(), hidden_states=hidden, audio_hidden_states=audio_hidden)
+            return AF3Output(loss=loss, logits=_logits(), hidden_states=hidden, audio_hidden_states=audio_hidden, token_logprobs=token_logprobs,
+                             token_entropy=token_entropy)
         # labels given: the reference returns logits beside the loss (modeling_audioflamingo3.py:625-642); here they are built on first access -
         # from the DETACHED final hidden states (no second autograd branch, the step's graph is not kept alive by the output object) and only while
         # the weights are still the ones the loss was computed with: after an optimizer step the lm_head has moved, the logits would no longer
@@ -735,7 +770,8 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, AfkDecodeForwar
                 xf = F_.DecoderLayerFn.apply(x_keep, *last_args)
                 return _logits(F_.RMSNormFn.apply(xf, self._anchor(lm + "norm.weight"), a, lm + "norm.weight", self.rms_eps))
 
-        return AF3Output(loss=loss, logits_fn=_lazy_logits, hidden_states=hidden, audio_hidden_states=audio_hidden)
+        return AF3Output(loss=loss, logits_fn=_lazy_logits, hidden_states=hidden, audio_hidden_states=audio_hidden, token_logprobs=token_logprobs,
+                         token_entropy=token_entropy)
 
     # ------------------------------------------------------------------ generate (greedy; KV cache - SURVEY.md 8(f)-4)
     def _merged_embeddings(self, ids, input_features, input_features_mask):
@@ -755,6 +791,7 @@ class AudioFlamingo3ForConditionalGeneration(AfkGenerationMixin, AfkDecodeForwar
                 src = torch.where(src >= 0, row.to(torch.int32), src).contiguous()
         return ops.embed_scatter_fwd(ids_flat, src, a[lm + "embed_tokens.weight"].data, audio)
 
+    _graphed_step = False   # set by graphs.GraphedTrainStep around its eager warm-up steps
     loss_on_valid_rows_only = True  # lm_head + CE (+ their backward GEMMs) on the rows with a label only (False: all B*S rows, as the reference)
     last_layer_rows_only = os.environ.get("AFK_LAST_LAYER_ROWS", "1") == "1"   # training forward with labels: the last decoder layer behind its attention on the labelled rows only
 

@@ -1263,6 +1263,38 @@ def ce_fwd_bwd_(logits, shift_labels, row_loss, denom, *, upstream=1.0, write_gr
               denom.data_ptr(), float(upstream), int(write_grad), _stream())
 
 
+def _chk_logprob_args(who, logits, shift_labels, vectors):
+    """logits: 2-D bf16 rows with unit inner stride; shift_labels int64 and every (name, fp32 vector) contiguous with one element per row"""
+    _chk(logits, BF16, f"{who} logits"), _chk(shift_labels, torch.int64, f"{who} shift_labels")
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise AfkError(f"{who} logits: a non-empty 2-D chunk with unit inner stride, got shape {tuple(logits.shape)} strides {tuple(logits.stride())}")
+    rows = logits.shape[0]
+    for name, t in (("shift_labels", shift_labels), *vectors):
+        if name != "shift_labels":
+            _chk(t, torch.float32, f"{who} {name}")
+        if t.dim() != 1 or t.shape[0] != rows or not t.is_contiguous():
+            raise AfkError(f"{who} {name}: a contiguous vector of {rows} elements (one per row of the chunk), got shape {tuple(t.shape)}")
+    return rows, logits.shape[1]
+
+
+def token_logprob(logits, shift_labels, logp, lse, entropy=None):
+    """per row of the bf16 chunk: logp = log_softmax(logits)[label], lse = logsumexp(logits), entropy (optional) = -sum p log p; an ignored row
+    (label < 0) gives 0 in all three.  The chunk is not written (afk_token_logprob; the contract is in include/afk.h).  -> logp"""
+    vectors = [("logp", logp), ("lse", lse)] + ([("entropy", entropy)] if entropy is not None else [])
+    rows, V = _chk_logprob_args("token_logprob", logits, shift_labels, vectors)
+    _lib.call("afk_token_logprob", logits.data_ptr(), logits.stride(0), rows, V, shift_labels.data_ptr(), logp.data_ptr(), lse.data_ptr(), _p(entropy),
+              _stream())
+    return logp
+
+
+def token_logprob_bwd_(logits, shift_labels, lse, u):
+    """in place on the RECOMPUTED chunk: logits <- bf16(u_row * (onehot(label) - exp(logits - lse_row))), u = d L / d logp per row; an ignored row
+    becomes zeros whatever u holds (afk_token_logprob_bwd).  -> logits"""
+    rows, V = _chk_logprob_args("token_logprob_bwd_", logits, shift_labels, [("lse", lse), ("u", u)])
+    _lib.call("afk_token_logprob_bwd", logits.data_ptr(), logits.stride(0), rows, V, shift_labels.data_ptr(), lse.data_ptr(), u.data_ptr(), _stream())
+    return logits
+
+
 def loss_reduce(row_loss, denom, loss, *, accumulate=False):
     _lib.call("afk_loss_reduce", row_loss.data_ptr(), row_loss.numel(), denom.data_ptr(), loss.data_ptr(), int(accumulate),
               _stream())

@@ -222,7 +222,7 @@ class _Stage:
                                f"give the stage a key_state()")
         c["fwd_meta"] = fwd_meta
         c["src"] = src
-        c["out_spec"] = [(tuple(t.shape), t.dtype) for t in outs]
+        c["out_spec"] = [(tuple(t.shape), t.dtype, t.device) for t in outs]   # device: a stage may keep a host-side scalar (LMHeadLogprobFn: the arena version)
         return outs
 
     def _fwd_fake(self, *a):
@@ -231,7 +231,7 @@ class _Stage:
         if c is None:
             raise RuntimeError(f"afk::{self.name}: run the step eagerly once before tracing it (output shapes are recorded per stage geometry)")
         _PINNED.add(key)   # traced: the compiled step will call _fwd_impl / _bwd_impl with this very string for as long as it lives
-        return [params.new_empty(shape, dtype=dtype) for shape, dtype in c["out_spec"]]
+        return [params.new_empty(shape, dtype=dtype, device=device) for shape, dtype, device in c["out_spec"]]
 
     # ------------------------------------------------------------------ autograd registration
     def _setup_context(self, ctx, inputs, output):

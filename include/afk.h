@@ -737,6 +737,18 @@ int afk_ce_fwd_bwd(void* logits, int64_t ld, int64_t rows, int V, const int64_t*
                    const float* denom, float upstream, int write_grad, void* stream);
 int afk_count_valid(const int64_t* labels, int64_t n, float* out, void* stream);
 int afk_loss_reduce(const float* row_loss, int64_t n, const float* denom, float* loss, int accumulate, void* stream);
+/* ---- per-token log-probabilities: log_softmax(logits.float(), -1).gather(-1, labels) without the fp32 tensor, differentiable per row ----
+ * The second loss-head stage (functional.LMHeadLogprobFn).  logits chunk [rows, V] bf16, rows ld apart (ld % 8 == 0, 16-byte aligned), only the
+ * first V columns are read or written; shift_labels int64, < 0 = ignored row.  -inf logits as for afk_ce_fwd_bwd.  Both deterministic.
+ * afk_token_logprob: ONE sweep, the chunk is not written.  logp[r] = logits[r][label] - lse[r] (bit-equal to -row_loss of
+ *   afk_ce_fwd_bwd(write_grad = 0)), lse[r] = logsumexp(logits[r]), entropy[r] (may be NULL) = -sum p log p, accumulated on the shifted values
+ *   x - max in the same sweep (a common offset of the row cancels exactly).  An ignored row gives 0 in all three.
+ * afk_token_logprob_bwd: ONE sweep over the RECOMPUTED chunk with the lse the forward saved, in place:
+ *   logits[r][c] <- bf16(upstream[r] * (onehot(label)[c] - exp(logits[r][c] - lse[r]))); an ignored row is written as zeros and upstream[r] is not read. */
+int afk_token_logprob(const void* logits, int64_t ld, int64_t rows, int V, const int64_t* shift_labels, float* logp, float* lse,
+                      float* entropy, void* stream);
+int afk_token_logprob_bwd(void* logits, int64_t ld, int64_t rows, int V, const int64_t* shift_labels, const float* lse,
+                          const float* upstream, void* stream);
 
 /* ---- log-mel frontend: WhisperFeatureExtractor._torch_extract_fbank_features, feature_extraction_whisper.py:135-168
  * wav [W, nsamp] fp32 -> out [W, nmel, nsamp/160] (fp32 or bf16).  cosb/sinb = hann-folded DFT basis
