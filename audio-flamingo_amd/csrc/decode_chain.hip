@@ -39,7 +39,7 @@ struct ChainArgs {
     float eps;
     const bf16* W;        // [N, K] row-major (nn.Linear layout)
     int64_t ldw;
-    const uint8_t* Wq;    // W8 (gemv_chain_kernel only): the weights as OCP e4m3fn codes [N][ld_wq] in place of W ...
+    const uint8_t* Wq;    // W8 (gemv_chain_kernel, gemv_chain_mfma_kernel): the weights as OCP e4m3fn codes [N][ld_wq] in place of W ...
     int64_t ld_wq;
     const float* wscale;  // ... and the fp32 scale of every output row [N]: row r of the Linear is wscale[r] * code
     int N, K;
@@ -525,6 +525,13 @@ __global__ __launch_bounds__(64 * (S > 4 ? S : 4)) void gemv_chain_batched_kerne
     }
 }
 
+// eight OCP e4m3fn codes (two 32-bit words, lowest byte first) -> eight bf16, exact: v_cvt_scalef32_pk_bf16_fp8 converts the two codes of a half-word per instruction
+__device__ __forceinline__ bf16x8 fp8x8_to_bf16(uint32_t u0, uint32_t u1) {
+    const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(u0, 1.f, false), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(u0, 1.f, true);
+    const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(u1, 1.f, false), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(u1, 1.f, true);
+    return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
 // The batched form on the matrix pipe.  With 8 input rows the dot-product form above issues 256 v_dot2 per 8 KiB of weights and wave - it is VALU-bound at
 // ~5 TB/s (gate|up 53.6 us against 42.5 us for one row).  v_mfma_f32_32x32x16_bf16 does the same contraction for 32 weight rows x up to 32 input rows in 32
 // cycles per KiB of weights and wave.  A group = 32 output rows (two runs of 16); S waves of a block split K into contiguous slices of 64-element blocks.
@@ -541,13 +548,27 @@ __global__ __launch_bounds__(64 * (S > 4 ? S : 4)) void gemv_chain_batched_kerne
 // COOPERATIVELY (lane -> row lane >> 3, 16-byte piece lane & 7: every lane carries real data), normalises them (cast before the weight multiply), parks the bf16
 // rows in a wave-private LDS strip and reads the MFMA's B fragments back from there (LDS operations of one wave execute in order): 2 NB loads and ~40 VALU
 // instructions per block instead of 4 masked fragment loads per block and a kernel launch per norm.
-template <int EPI, int S, int RG, int PRO = PRO_PLAIN>
+//
+// W8 (generate(decode_weights="fp8", decode_weights_batched=True)): the same kernel on FP8 weights - OCP e4m3fn codes with one fp32 scale per output row
+// (afk_quantize_rows_fp8), half the streamed bytes.  A lane's 16-byte load carries 16 codes, so a row-contiguous load instruction (8 rows x 128 bytes) covers TWO
+// 64-element blocks of its rows - lane -> row lane >> 3, block (lane & 7) >> 2, 16-code piece lane & 3 - and a stage (the SAME NB blocks per wave as on bf16: same K
+// partition, so the same sums) is four load instructions instead of eight.  Where a wave's last pair has one block only (K % 128 == 64) the lanes of the missing block
+// repeat the row's last block: nothing behind column K is read, and what they park lies in a block slot the MFMAs skip.  The codes are widened in front of the LDS
+// park - e4m3fn -> bf16 is exact; v_cvt_scalef32_pk_bf16_fp8 with scale 1 writes a bf16 PAIR per instruction (8 VALU instructions per load; v_cvt_pk_f32_fp8 + a
+// v_perm_b32 pack would be 16) - into two 16-byte pieces of the bf16 layout, so the swizzle, the fragment reads and the MFMA are what they were.  The lanes of a
+// pair's second block park their upper piece first: the eight lanes of a row then write eight different pieces per store, as the bf16 stores do.  The row scale
+// multiplies the finished fp32 sum (requested at the top of the kernel) in front of the bias add and the first bf16 rounding.
+template <int EPI, int S, int RG, int PRO = PRO_PLAIN, bool W8 = false>
 __global__ __launch_bounds__(64 * S) void gemv_chain_mfma_kernel(ChainArgs p) {
     constexpr int R = RG, HR = RG / 2, MBX = AFK_CHAIN_BATCH_MAX;
     constexpr int JR = RG / 8;          // load instructions per 64-element block (8 rows x 128 bytes each)
     constexpr int NB = 8 / JR;          // blocks per stage: eight loads in flight per register set either way
     constexpr int BLK = RG * 128;       // bytes of a staged block
+    constexpr int NLD = W8 ? 4 : 8;     // load instructions per stage
+    using WT = std::conditional_t<W8, uint8_t, bf16>;
+    using GV = std::conditional_t<W8, u32x4, bf16x8>;
     static_assert(S >= 4 && S <= 16 && (RG == 32 || RG == 16), "256 finishing threads; S x 8 KiB of (dynamic) LDS");
+    static_assert(!W8 || ((PRO == PRO_RMS || PRO == PRO_PLAIN_LDS) && EPI != EPI_RESID_NORM), "FP8 weights: the norm-in-prologue / LDS-strip launches");
     extern __shared__ __attribute__((aligned(16))) char stage_dyn[];
     char(*stage)[8192] = (char(*)[8192])stage_dyn;
     const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
@@ -572,6 +593,11 @@ __global__ __launch_bounds__(64 * S) void gemv_chain_mfma_kernel(ChainArgs p) {
         rA = R * g;
         rB = rA + HR;
     }
+    float e_scale = 1.f;   // W8: the scale of the row this thread finishes, requested ahead of everything else
+    if constexpr (W8) {
+        const int er = (threadIdx.x / MBX) & (R - 1);
+        e_scale = p.wscale[er < HR ? rA + er : rB + er - HR];
+    }
     // this wave's K slice in blocks of 64 elements (K % 64 == 0)
     const int nkb = p.K >> 6;
     // K split over the S waves: contiguous slices (p.kil == 0: wave w owns blocks [w per, (w + 1) per)), or stages dealt round-robin (p.kil == 1: wave w owns the
@@ -581,30 +607,63 @@ __global__ __launch_bounds__(64 * S) void gemv_chain_mfma_kernel(ChainArgs p) {
     const int STEP = p.kil ? S * NB : NB;   // blocks from one stage of this wave to its next
     // global side: load j of a block covers group rows 8 j + (lane >> 3), 16-byte piece lane & 7
     const int rowl = lane >> 3, piece = lane & 7;
-    const bf16* wp[JR];
+    const WT* wp[JR];
     uint32_t wr_off[JR];
     char* my = &stage[w][0];
 #pragma unroll
     for (int j = 0; j < JR; ++j) {
         const int r = 8 * j + rowl;
-        wp[j] = p.W + (int64_t)(r < HR ? rA + r : rB + r - HR) * p.ldw + piece * 8;
-        wr_off[j] = r * 128 + ((piece ^ ((r >> 1) & 7)) << 4);
+        if constexpr (W8) {   // codes: block piece >> 2 of the pair, 16-code piece (piece & 3) = bf16 pieces 2 (piece & 3) and + 1; the second block's lanes park the upper one first
+            wp[j] = p.Wq + (int64_t)(r < HR ? rA + r : rB + r - HR) * p.ld_wq + (piece & 3) * 16;
+            wr_off[j] = (piece >> 2) * BLK + r * 128 + (((2 * (piece & 3) + (piece >> 2)) ^ ((r >> 1) & 7)) << 4);
+        } else {
+            wp[j] = p.W + (int64_t)(r < HR ? rA + r : rB + r - HR) * p.ldw + piece * 8;
+            wr_off[j] = r * 128 + ((piece ^ ((r >> 1) & 7)) << 4);
+        }
     }
     const int fr = l31 & (RG - 1);
     const uint32_t rd_row = fr * 128, rd_swz = (fr >> 1) & 7;
     const bf16* xp = p.x + (int64_t)min(l31, p.M - 1) * p.ldx + hi * 8;
-    auto gload = [&](bf16x8(&dst)[8], int kb) {   // NB blocks; a block past the slice repeats the slice's last one (valid memory) and is skipped below
+    auto gload = [&](GV(&dst)[NLD], int kb) {   // NB blocks; a block past the slice repeats the slice's last one (valid memory) and is skipped below
+        if constexpr (W8) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const int kk = min(kb + b, b1 - 1) << 6;
+            for (int pr = 0; pr < NB / 2; ++pr) {   // a load = the two blocks of a pair; 64 codes = 64 bytes per block and row
+                const int kk = min(kb + 2 * pr + (piece >> 2), b1 - 1) << 6;
 #pragma unroll
-            for (int j = 0; j < JR; ++j) dst[b * JR + j] = __builtin_nontemporal_load((const bf16x8*)(wp[j] + kk));
+                for (int j = 0; j < JR; ++j) dst[pr * JR + j] = __builtin_nontemporal_load((const u32x4*)(wp[j] + kk));
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                const int kk = min(kb + b, b1 - 1) << 6;
+#pragma unroll
+                for (int j = 0; j < JR; ++j) dst[b * JR + j] = __builtin_nontemporal_load((const bf16x8*)(wp[j] + kk));
+            }
+        }
+    };
+    auto park = [&](const GV(&cur)[NLD]) {   // a stage's weights into this wave's staging area, as bf16
+        if constexpr (W8) {
+            const bool up = piece >= 4;
+#pragma unroll
+            for (int pr = 0; pr < NB / 2; ++pr)
+#pragma unroll
+                for (int j = 0; j < JR; ++j) {
+                    const u32x4 c = cur[pr * JR + j];
+                    const uint32_t o = 2 * pr * BLK + wr_off[j];
+                    *(bf16x8*)(my + o) = fp8x8_to_bf16(up ? c[2] : c[0], up ? c[3] : c[1]);
+                    *(bf16x8*)(my + (o ^ 16)) = fp8x8_to_bf16(up ? c[0] : c[2], up ? c[1] : c[3]);
+                }
+        } else {
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+#pragma unroll
+                for (int j = 0; j < JR; ++j) *(bf16x8*)(my + b * BLK + wr_off[j]) = cur[b * JR + j];
         }
     };
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    bf16x8 ga[8], gb[8];
+    GV ga[NLD], gb[NLD];
     // ---- PRO_RMS: strip of normalised rows [NB blocks][8 rows][128 B] behind the S weight stages, and the row statistic
     constexpr int HXB = NB * 1024;
     char* hx = stage_dyn + S * 8192 + w * HXB;
@@ -726,14 +785,11 @@ __global__ __launch_bounds__(64 * S) void gemv_chain_mfma_kernel(ChainArgs p) {
             xa[i][e] = (bf16)0.f;
             if (HOIST) xb[i][e] = (bf16)0.f;
         }
-    auto consume = [&](bf16x8(&cur)[8], bf16x8(&nxt)[8], int kb) {
+    auto consume = [&](GV(&cur)[NLD], GV(&nxt)[NLD], int kb) {
         xload2(xa, kb);                              // ahead of the next stage's weight loads: loads return in order
         if constexpr (HOIST) xload2(xb, kb + 2);
         if (kb + STEP < b1) gload(nxt, kb + STEP);
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int j = 0; j < JR; ++j) *(bf16x8*)(my + b * BLK + wr_off[j]) = cur[b * JR + j];
+        park(cur);
         mma2(xa, kb, 0);
         if constexpr (HOIST) {
             mma2(xb, kb, 2);
@@ -746,7 +802,7 @@ __global__ __launch_bounds__(64 * S) void gemv_chain_mfma_kernel(ChainArgs p) {
         if constexpr (PRO == PRO_PLAIN_LDS) {
             if (b0 < b1) gload(ga, b0);
         }
-        auto consumeN = [&](bf16x8(&cur)[8], bf16x8(&nxt)[8], int kb) {
+        auto consumeN = [&](GV(&cur)[NLD], GV(&nxt)[NLD], int kb) {
             bf16x8 xr[NB], gw[NB];
 #pragma unroll
             for (int b = 0; b < NB; ++b) {   // ahead of the next stage's weight loads: loads return in order
@@ -755,10 +811,7 @@ __global__ __launch_bounds__(64 * S) void gemv_chain_mfma_kernel(ChainArgs p) {
                 if constexpr (PRO == PRO_RMS) gw[b] = *(const bf16x8*)(p.normw + kk + xpc * 8);
             }
             if (kb + STEP < b1) gload(nxt, kb + STEP);
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-#pragma unroll
-                for (int j = 0; j < JR; ++j) *(bf16x8*)(my + b * BLK + wr_off[j]) = cur[b * JR + j];
+            park(cur);
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
                 bf16x8 h = xr[b];
@@ -891,6 +944,7 @@ __global__ __launch_bounds__(64 * S) void gemv_chain_mfma_kernel(ChainArgs p) {
     float tot = 0.f;
 #pragma unroll
     for (int q = 0; q < S; ++q) tot += ((const float*)&stage[q][0])[r * MBX + m];   // K slices summed in slice order
+    if constexpr (W8) tot *= e_scale;       // the row's scale on the finished fp32 sum, in front of the bias add and the first bf16 rounding
     float* fin = (float*)&stage[0][4096];   // [R][MBX], nobody's sums live there
     const int row = r < HR ? rA + r : rB + r - HR;
     const bool valid = m < p.M;
@@ -1480,22 +1534,24 @@ extern "C" int afk_decode_chain_linear_residual_batched(const void* x, int64_t l
 
 // ---------------------------------------------------------------- 1 .. 8 sequences, RMSNorm in the Linear's own prologue (matrix-pipe form only, round 6)
 namespace {
-template <int EPI, int S>
+template <int EPI, int S, bool W8 = false>
 int launch_chain_norm(ChainArgs p, int rows, hipStream_t st) {
     constexpr int NBX = 2;   // 32-row groups: two 64-element blocks per stage
     constexpr int LDS = S * 8192 + S * NBX * 1024;
     p.kil = 1;
-    if (p.M > 2 * AFK_CHAIN_BATCH_MAX) return launch_chain_ng<EPI, S, 32, PRO_RMS, 4>(p, rows, st);   // 17 .. 32 sequences: four groups of eight
-    if (p.M > AFK_CHAIN_BATCH_MAX) return launch_chain_ng<EPI, S, 32, PRO_RMS, 2>(p, rows, st);       // 9 .. 16: two
+    if constexpr (!W8) {     // FP8 weights: 1 .. 8 sequences (the entry points refuse more)
+        if (p.M > 2 * AFK_CHAIN_BATCH_MAX) return launch_chain_ng<EPI, S, 32, PRO_RMS, 4>(p, rows, st);   // 17 .. 32 sequences: four groups of eight
+        if (p.M > AFK_CHAIN_BATCH_MAX) return launch_chain_ng<EPI, S, 32, PRO_RMS, 2>(p, rows, st);       // 9 .. 16: two
+    }
     static bool attr_set = false;
     if (LDS > 65536 && !attr_set) {
-        hipFuncSetAttribute((const void*)gemv_chain_mfma_kernel<EPI, S, 32, PRO_RMS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        hipFuncSetAttribute((const void*)gemv_chain_mfma_kernel<EPI, S, 32, PRO_RMS, W8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         attr_set = true;
     }
     static const int ssf = [] { const char* e = getenv("AFK_CHAIN_SS_FIRST"); return e && e[0] == '0' ? 0 : 1; }();
     p.kil = 1;
     p.ss_first = ssf;
-    hipLaunchKernelGGL((gemv_chain_mfma_kernel<EPI, S, 32, PRO_RMS>), dim3((unsigned)(rows / 32)), dim3(64 * S), LDS, st, p);
+    hipLaunchKernelGGL((gemv_chain_mfma_kernel<EPI, S, 32, PRO_RMS, W8>), dim3((unsigned)(rows / 32)), dim3(64 * S), LDS, st, p);
     return AFK_OK;
 }
 }  // namespace
@@ -1579,6 +1635,84 @@ extern "C" int afk_decode_chain_linear_residual_ss_batched(const void* x, int64_
     AFK_LAUNCH_CHECK("afk_decode_chain_linear_residual_ss_batched");
     return AFK_OK;
 }
+
+// ---------------------------------------------------------------- the four launches of the default 2 .. 8-row step on FP8 weights (W8: e4m3fn codes + one fp32 scale per output row)
+// what the bf16 twins ask of W / ldw, asked of the codes (a lane's load is 16 bytes = 16 codes), and 1 .. 8 rows: the 9 .. 32-row forms read bf16 weights only
+#define AFK_W8B_REQUIRE(name, M, Wq, ld_wq, wscale, K)                                                                                                      \
+    AFK_REQUIRE((M) >= 1 && (M) <= AFK_CHAIN_BATCH_MAX && (Wq) && (wscale) && (K) > 0 && (K) % 64 == 0 && (ld_wq) >= (K) && (ld_wq) % 16 == 0 &&            \
+                    ((uintptr_t)(Wq) & 15) == 0,                                                                                                            \
+                name ": FP8 weights need 1 <= M <= 8, K %% 64 == 0, ld_wq %% 16 == 0, 16-byte-aligned rows and a scale per row")
+#define AFK_SS_REQUIRE(name, ss_part, ss_nparts)                                                                                       \
+    AFK_REQUIRE(!(ss_part) || ((ss_nparts) > 0 && (ss_nparts) <= 256 && (ss_nparts) % 4 == 0 && (uintptr_t)(ss_part) % 16 == 0),      \
+                name ": 4 .. 256 partial sums per row, a multiple of 4, 16-byte aligned")
+
+extern "C" int afk_decode_chain_qkv_norm_batched_w8(const void* x, int64_t ldx, int M, const void* norm_w, float eps, const void* Wq, int64_t ld_wq, const float* wscale,
+                                                    int K, const void* bias, const void* cos_t, const void* sin_t, const int* pos, void* q_out, int64_t ldq, void* kcache,
+                                                    int64_t k_bs, void* vtcache, int64_t vt_bs, int spad, const int* start_dev, int Hq, int Hkv, int D,
+                                                    const float* ss_part, int ss_nparts, void* stream) {
+    AFK_REQUIRE(x && norm_w && bias && cos_t && sin_t && pos && q_out && kcache && vtcache && start_dev, "afk_decode_chain_qkv_norm_batched_w8: null pointer");
+    AFK_SS_REQUIRE("afk_decode_chain_qkv_norm_batched_w8", ss_part, ss_nparts);
+    AFK_W8B_REQUIRE("afk_decode_chain_qkv_norm_batched_w8", M, Wq, ld_wq, wscale, K);
+    AFK_REQUIRE(ldx % 8 == 0 && Hq > 0 && Hkv > 0 && (D / 2) % 16 == 0 && (Hkv * D) % 32 == 0 && ((Hq + 2 * Hkv) * D) % 32 == 0 && spad > 0,
+                "afk_decode_chain_qkv_norm_batched_w8: unsupported shape (head_dim %% 32 == 0)");
+    ChainArgs p = {};
+    p.x = (const bf16*)x; p.ldx = ldx; p.M = M; p.normw = (const bf16*)norm_w; p.eps = eps; p.Wq = (const uint8_t*)Wq; p.ld_wq = ld_wq; p.wscale = wscale;
+    p.N = (Hq + 2 * Hkv) * D; p.K = K;
+    p.bias = (const bf16*)bias; p.cos_t = (const bf16*)cos_t; p.sin_t = (const bf16*)sin_t; p.pos = pos; p.pos_stride = 1; p.start = start_dev;
+    p.q_out = (bf16*)q_out; p.ldq = ldq; p.Kc = (bf16*)kcache; p.k_bs = k_bs; p.Vt = (bf16*)vtcache; p.vt_bs = vt_bs; p.spad = spad; p.Hq = Hq; p.Hkv = Hkv; p.D = D;
+    p.ss_in = ss_part; p.ss_nparts = ss_part ? ss_nparts : 0;
+    launch_chain_norm<EPI_QKV, 8, true>(p, p.N, ST);
+    AFK_LAUNCH_CHECK("afk_decode_chain_qkv_norm_batched_w8");
+    return AFK_OK;
+}
+
+extern "C" int afk_decode_chain_gate_up_norm_batched_w8(const void* x, int64_t ldx, int M, const void* norm_w, float eps, const void* Wq, int64_t ld_wq,
+                                                        const float* wscale, int I, int K, void* act_out, int64_t ld_act, const float* ss_part, int ss_nparts,
+                                                        void* stream) {
+    AFK_SS_REQUIRE("afk_decode_chain_gate_up_norm_batched_w8", ss_part, ss_nparts);
+    AFK_W8B_REQUIRE("afk_decode_chain_gate_up_norm_batched_w8", M, Wq, ld_wq, wscale, K);
+    AFK_REQUIRE(x && norm_w && act_out && I > 0 && I % 16 == 0 && ldx % 8 == 0, "afk_decode_chain_gate_up_norm_batched_w8: unsupported shape (I %% 16 == 0)");
+    ChainArgs p = {};
+    p.x = (const bf16*)x; p.ldx = ldx; p.M = M; p.normw = (const bf16*)norm_w; p.eps = eps; p.Wq = (const uint8_t*)Wq; p.ld_wq = ld_wq; p.wscale = wscale;
+    p.N = 2 * I; p.K = K; p.out = (bf16*)act_out; p.ld_out = ld_act; p.D = 2; p.ss_in = ss_part; p.ss_nparts = ss_part ? ss_nparts : 0;
+    launch_chain_norm<EPI_SWIGLU, 4, true>(p, 2 * I, ST);
+    AFK_LAUNCH_CHECK("afk_decode_chain_gate_up_norm_batched_w8");
+    return AFK_OK;
+}
+
+extern "C" int afk_decode_chain_lm_head_norm_batched_w8(const void* x, int64_t ldx, int M, const void* norm_w, float eps, const void* Wq, int64_t ld_wq,
+                                                        const float* wscale, int N, int K, float* logits, int64_t ld_logits, const float* ss_part, int ss_nparts,
+                                                        void* stream) {
+    AFK_SS_REQUIRE("afk_decode_chain_lm_head_norm_batched_w8", ss_part, ss_nparts);
+    AFK_W8B_REQUIRE("afk_decode_chain_lm_head_norm_batched_w8", M, Wq, ld_wq, wscale, K);
+    AFK_REQUIRE(x && norm_w && logits && N > 0 && N % 32 == 0 && ldx % 8 == 0, "afk_decode_chain_lm_head_norm_batched_w8: unsupported shape (N %% 32 == 0)");
+    ChainArgs p = {};
+    p.x = (const bf16*)x; p.ldx = ldx; p.M = M; p.normw = (const bf16*)norm_w; p.eps = eps; p.Wq = (const uint8_t*)Wq; p.ld_wq = ld_wq; p.wscale = wscale;
+    p.N = N; p.K = K; p.out_f32 = logits; p.ld_out = ld_logits; p.D = 2; p.ss_in = ss_part; p.ss_nparts = ss_part ? ss_nparts : 0;
+    launch_chain_norm<EPI_LOGITS, 4, true>(p, N, ST);
+    AFK_LAUNCH_CHECK("afk_decode_chain_lm_head_norm_batched_w8");
+    return AFK_OK;
+}
+
+extern "C" int afk_decode_chain_linear_residual_ss_batched_w8(const void* x, int64_t ldx, int M, const void* Wq, int64_t ld_wq, const float* wscale, int N, int K,
+                                                              const void* residual, int64_t ld_res, void* out, int64_t ld_out, float* ss_part, void* stream) {
+    AFK_W8B_REQUIRE("afk_decode_chain_linear_residual_ss_batched_w8", M, Wq, ld_wq, wscale, K);
+    AFK_REQUIRE(x && residual && out && ss_part && N > 0 && N % 64 == 0 && ldx % 8 == 0, "afk_decode_chain_linear_residual_ss_batched_w8: bad arguments (N %% 64 == 0)");
+    ChainArgs p = {};
+    p.x = (const bf16*)x; p.ldx = ldx; p.M = M; p.Wq = (const uint8_t*)Wq; p.ld_wq = ld_wq; p.wscale = wscale; p.N = N; p.K = K;
+    p.residual = (const bf16*)residual; p.ld_res = ld_res; p.out = (bf16*)out; p.ld_out = ld_out; p.D = 2; p.ss_out = ss_part; p.kil = 1;
+    constexpr int LDS = 8 * 8192 + 8 * 4 * 1024;   // the input rows through the LDS strip, as the bf16 twin's default form
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipFuncSetAttribute((const void*)gemv_chain_mfma_kernel<EPI_RESID, 8, 16, PRO_PLAIN_LDS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((gemv_chain_mfma_kernel<EPI_RESID, 8, 16, PRO_PLAIN_LDS, true>), dim3((unsigned)(N / 16)), dim3(512), LDS, ST, p);
+    AFK_LAUNCH_CHECK("afk_decode_chain_linear_residual_ss_batched_w8");
+    return AFK_OK;
+}
+#undef AFK_SS_REQUIRE
+#undef AFK_W8B_REQUIRE
 
 // Linear + residual + the RMSNorm that follows, 1 .. 8 sequences, always on the matrix-pipe form (16-row groups x 8 K slices): out = bf16(W x) + residual,
 // h_out = norm_w * bf16(out * rsqrt(mean(out^2) + eps)) written by the last block of the launch to arrive (EPI_RESID_NORM above).  counter: one zero-initialised int32.

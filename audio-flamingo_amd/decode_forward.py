@@ -126,6 +126,7 @@ class AfkDecodeForwardMixin:
     decode_norm_mode = os.environ.get("AFK_DECODE_NORM", "prologue")   # batched decode, four sequences and more: "prologue" | "producer" | "launch" (_decode_layers_chain_batched)
     decode_chain_batch = int(os.environ.get("AFK_DECODE_CHAIN_BATCH", "8"))   # largest batch the one-launch-per-Linear kernels take (0: single sequence only)
     decode_weight_dtype = os.environ.get("AFK_DECODE_WEIGHTS", "bf16")   # generate(decode_weights=None): "bf16" | "fp8" - the single-sequence chain on the FP8 copy of its weights (decode_w8.py)
+    decode_weights_batched = os.environ.get("AFK_DECODE_WEIGHTS_BATCHED", "0") == "1"   # generate(decode_weights_batched=None): with "fp8", steps of 2 - 8 rows (batches, copies, beams, guidance, lookup verification, a shared prompt) read the FP8 copy too (afk_decode_chain_*_batched_w8)
     _w8 = None   # the FP8 copy (decode_w8.DecodeW8): built by quantize_decode_weights() / the first fp8 call, None until then and after drop_decode_weights()
     last_w8_stats = None   # the last generate() call that decoded on the FP8 copy: decode_w8.stats; None after every other call
     decode_splits = 8  # key-range splits of the Q = 1 attention (0: use the interval MFMA kernel instead)
@@ -383,16 +384,25 @@ class AfkDecodeForwardMixin:
         self.last_w8_stats = _w8mod.stats(self._w8, rebuilt)
         return self._w8
 
-    def _w8_resolve(self, decode_weights, rows, num_beams, copies, guidance, lookup, share_prompt, use_cache, exact_fp32, assist=False):
-        """decode_w8.resolve with what only the model knows: the geometry"""
+    def _w8_resolve(self, decode_weights, rows, num_beams, copies, guidance, lookup, share_prompt, use_cache, exact_fp32, assist=False, batched=None, lookup_rows=None):
+        """decode_w8.resolve with what only the model knows: the geometry, and (batched: the keyword, None: the class attribute decode_weights_batched) whether a
+        step of that many rows runs the norm-in-prologue launches.  lookup_rows: the k + 1 rows of a prompt-lookup verify forward"""
         on = (self.decode_weight_dtype if decode_weights is None else decode_weights) == "fp8"
-        chain_ok = widths_ok = head_ok = True
+        chain_ok = widths_ok = head_ok = batched_ok = True
+        step_rows = None
         if on:   # asked only where the answer is read: with the switch off the call reads no attribute it did not read before
             chain_ok = self._chain_ok(1)
             widths_ok = self.H % 16 == 0 and (self.Hq * self.D) % 16 == 0 and self.I % 16 == 0
-            head_ok = self.arena["lm_head.weight"].data.shape[0] % 8 == 0
+            head = self.arena["lm_head.weight"].data
+            head_ok = head.shape[0] % 8 == 0
+            batched = bool(self.decode_weights_batched if batched is None else batched)
+            if batched:
+                step_rows = int(lookup_rows) if lookup else int(rows) * max(int(num_beams), 1) * (2 if guidance else 1)
+                batched_ok = (self.decode_norm_mode == "prologue" and self.decode_mfma_from <= step_rows <= self.decode_prologue_max
+                              and self._prologue_shapes_ok(head) and self._chain_batched_ok(step_rows, head))
         return _w8mod.resolve(decode_weights, self.decode_weight_dtype, rows=rows, num_beams=num_beams, copies=copies, guidance=guidance, lookup=lookup,
-                              share_prompt=share_prompt, use_cache=use_cache, exact_fp32=exact_fp32, chain_ok=chain_ok, widths_ok=widths_ok, head_ok=head_ok, assist=assist)
+                              share_prompt=share_prompt, use_cache=use_cache, exact_fp32=exact_fp32, chain_ok=chain_ok, widths_ok=widths_ok, head_ok=head_ok, assist=assist,
+                              batched=bool(on and batched), step_rows=step_rows, batched_ok=batched_ok)
 
     def _chain_layers(self, x, cache, pos_rows, krange, start_dev, aws=None, w8=None):
         """one new position of ONE sequence: five launches per decoder layer (round 4; ten on the split-K + glue path above).  Every Linear is one
@@ -475,7 +485,7 @@ class AfkDecodeForwardMixin:
             return logits
         return ops.rmsnorm_fwd(x, self.arena[self._lm + "norm.weight"].data, self.rms_eps)[0]
 
-    def _decode_layers_chain_batched(self, x, B, cache, pos_rows, krange, start_dev, aws, head, one_sequence=False, shared=None):
+    def _decode_layers_chain_batched(self, x, B, cache, pos_rows, krange, start_dev, aws, head, one_sequence=False, shared=None, w8=None):
         """one new position of 2 .. 32 sequences: the single-sequence chain with M input rows per launch (`afk_decode_chain_*_batched`: the weights are still
         read once per step).  Round 6: 2 .. 8 sequences take the RMSNorm in the prologue of the Linear that consumes it (5 launches per layer), 9 .. 32 run as
         groups of eight behind one norm launch per norm (7 per layer); geometries the matrix-pipe launches do not take keep rounds 4-5's form (7 launches per
@@ -483,8 +493,12 @@ class AfkDecodeForwardMixin:
         prompt-lookup decoding): row m lands in slot *start_dev + m and every row reads the same cache (CacheGeometry's k_write .. vt_read).
         shared (a decode_share.SharedPrompt): `cache` is the TAIL cache of the B = B0 * n continuations - the qkv launch appends to it as it is told to - and
         the attention launch is afk_attn_decode_shared over the prompt cache (prompt keys shared.prange) and the tail (krange = [B, 2]: the tail keys);
-        aws is its workspace.  Nothing else in the loop differs.  -> fp32 logits [B, V]"""
+        aws is its workspace.  Nothing else in the loop differs.
+        w8 (a decode_w8.DecodeW8; generate() resolved 2 - 8 rows on the norm-in-prologue launches): the four Linears and the lm_head stream its FP8 codes and
+        row scales (afk_decode_chain_*_batched_w8); the attention launch, the ss buffers and everything else are the same.  -> fp32 logits [B, V]"""
         g, w = CacheGeometry.of(self, cache, one_sequence=one_sequence), self._w
+        if w8 is not None:
+            return self._decode_layers_chain_batched_w8(g, x, B, pos_rows, krange, start_dev, aws, head, shared, w8)
         Hq, Hkv, D, H, nq, eps, st, dev = g.Hq, g.Hkv, g.D, g.H, g.nq, g.eps, g.stream, x.device
         ns = self._decode_attn_ws_check(aws, B, g.Spad) if shared is None else shared.nsplit
         cos, sin, pos, start = g.cos.data_ptr(), g.sin.data_ptr(), pos_rows.data_ptr(), start_dev.data_ptr()
@@ -566,6 +580,51 @@ class AfkDecodeForwardMixin:
         _lib.call("afk_decode_chain_lm_head_batched", y.data_ptr(), y.stride(0), B, head.data_ptr(), head.stride(0), head.shape[0], H, logits.data_ptr(), head.shape[0], st)
         return logits
 
+    def _decode_layers_chain_batched_w8(self, g, x, B, pos_rows, krange, start_dev, aws, head, shared, w8):
+        """the "prologue" form of _decode_layers_chain_batched on the FP8 copy: the same five launches per layer and the lm_head launch, the Linears' weight
+        pointer and pitch replaced by codes, pitch and row scales"""
+        w = self._w
+        Hq, Hkv, D, H, nq, eps, st, dev = g.Hq, g.Hkv, g.D, g.H, g.nq, g.eps, g.stream, x.device
+        if not (self.decode_norm_mode == "prologue" and self.decode_mfma_from <= B <= min(self.decode_prologue_max, 8) and self._prologue_shapes_ok(head)):
+            raise AfkError(f"the FP8 batched decode chain takes the norm-in-prologue launches only (2 - 8 rows), not a step of {B} rows in mode {self.decode_norm_mode!r}")
+        ns = self._decode_attn_ws_check(aws, B, g.Spad) if shared is None else shared.nsplit
+        cos, sin, pos, start = g.cos.data_ptr(), g.sin.data_ptr(), pos_rows.data_ptr(), start_dev.data_ptr()
+        q = torch.empty((B, nq), device=dev, dtype=torch.bfloat16)
+        o = torch.empty((B, nq), device=dev, dtype=torch.bfloat16)
+        q8 = lambda t: (t.codes.data_ptr(), t.codes.stride(0), t.scale.data_ptr())
+        _p = lambda t: None if t is None else t.data_ptr()
+        ssx = None
+        for i in range(g.L):
+            lw = w8.layers[i]
+            _lib.call("afk_decode_chain_qkv_norm_batched_w8", x.data_ptr(), x.stride(0), B, w(i, "input_layernorm.weight").data_ptr(), eps, *q8(lw["self_attn.qkv.weight"]), H,
+                      w(i, "self_attn.qkv.bias").data_ptr(), cos, sin, pos, q.data_ptr(), nq, g.k(i), g.k_write, g.vt(i), g.vt_write, g.vt_row, start, Hq, Hkv, D, _p(ssx), H // 16, st)
+            if shared is None:
+                _lib.call("afk_attn_decode_fused", q.data_ptr(), nq, D, g.k(i), g.k_read, g.k_row, D, g.vt(i), g.vt_read, g.vt_row,
+                          o.data_ptr(), nq, D, krange.data_ptr(), B, Hq, Hkv, D, float(D ** -0.5), ns, aws.data_ptr(), st)
+            else:
+                Kp, Vtp = shared.cache
+                _lib.call("afk_attn_decode_shared", q.data_ptr(), nq, D, Kp[i].data_ptr(), shared.S0 * g.nk, g.nk, D, Vtp[i].data_ptr(), Hkv * D * Vtp.shape[4],
+                          Vtp.shape[4], shared.S0, g.k(i), g.k_sample, g.k_row, D, g.vt(i), g.vt_sample, g.vt_row, g.Smax, o.data_ptr(), nq, D,
+                          shared.prange.data_ptr(), krange.data_ptr(), B // shared.n, shared.n, Hq, Hkv, D, float(D ** -0.5), ns, aws.data_ptr(), aws.numel(), st)
+            x2 = torch.empty_like(x)
+            ss2 = torch.empty((1, 8, H // 16), device=dev, dtype=torch.float32)
+            _lib.call("afk_decode_chain_linear_residual_ss_batched_w8", o.data_ptr(), nq, B, *q8(lw["self_attn.o_proj.weight"]), H, nq, x.data_ptr(), x.stride(0), x2.data_ptr(), H,
+                      ss2.data_ptr(), st)
+            gu = lw["mlp.gate_up.weight"]
+            I = gu.codes.shape[0] // 2
+            act = torch.empty((B, I), device=dev, dtype=torch.bfloat16)
+            _lib.call("afk_decode_chain_gate_up_norm_batched_w8", x2.data_ptr(), x2.stride(0), B, w(i, "post_attention_layernorm.weight").data_ptr(), eps, *q8(gu), I, H,
+                      act.data_ptr(), I, ss2.data_ptr(), H // 16, st)
+            x = torch.empty_like(x2)
+            ssx = torch.empty((1, 8, H // 16), device=dev, dtype=torch.float32)
+            _lib.call("afk_decode_chain_linear_residual_ss_batched_w8", act.data_ptr(), I, B, *q8(lw["mlp.down_proj.weight"]), H, I, x2.data_ptr(), H, x.data_ptr(), H,
+                      ssx.data_ptr(), st)
+        h8 = w8.head
+        logits = torch.empty((B, h8.codes.shape[0]), device=dev, dtype=torch.float32)
+        _lib.call("afk_decode_chain_lm_head_norm_batched_w8", x.data_ptr(), x.stride(0), B, self.arena[self._lm + "norm.weight"].data.data_ptr(), eps, *q8(h8),
+                  h8.codes.shape[0], H, logits.data_ptr(), h8.codes.shape[0], _p(ssx), H // 16, st)
+        return logits
+
     # ------------------------------------------------------------------ which loop takes a step
     def _prologue_shapes_ok(self, head):
         """the norm-in-prologue matrix-pipe launches (afk_decode_chain_*_norm_batched / _linear_residual_ss_batched) take this geometry"""
@@ -599,7 +658,7 @@ class AfkDecodeForwardMixin:
             # tail keys are [0, cur + 1).  Only the batched chain has the route (generate() resolved that before the prefill)
             sh = st.shared
             sh.trange[:, 1:].copy_((st.cur + 1).expand(B, 1))
-            return self._decode_layers_chain_batched(x.contiguous(), B, st.cache, sh.pos0 + st.cur, sh.trange, st.cur, sh.ws, st.head, shared=sh)
+            return self._decode_layers_chain_batched(x.contiguous(), B, st.cache, sh.pos0 + st.cur, sh.trange, st.cur, sh.ws, st.head, shared=sh, w8=st.w8)
         if st.single is not None:   # single sequence (generate()): views of the step-state tensor, advanced by ONE add per step
             pos1, kr1 = st.single.pos1, st.single.kr1
         else:
@@ -608,7 +667,7 @@ class AfkDecodeForwardMixin:
         if self._chain_batched_ok(B, st.head):
             if st.aws is None:
                 st.aws = self._decode_attn_workspace(x.device, st.cache[1].shape[4], B)
-            return self._decode_layers_chain_batched(x.contiguous(), B, st.cache, pos1, kr1, st.cur, st.aws, st.head)
+            return self._decode_layers_chain_batched(x.contiguous(), B, st.cache, pos1, kr1, st.cur, st.aws, st.head, w8=st.w8)
         if self._chain_ok(B):
             if st.aws is None:
                 st.aws = self._decode_attn_workspace(x.device, st.cache[1].shape[4])
@@ -622,13 +681,13 @@ class AfkDecodeForwardMixin:
             y = self._decode_layers(x, B, 1, None, st.cache, pos1, kr1, False, start_dev=st.cur)
         return ops.gemm_nt(y, st.head).float()
 
-    def _lookup_forward(self, x, cache, pos_rows, krange, start_dev, aws, head):
+    def _lookup_forward(self, x, cache, pos_rows, krange, start_dev, aws, head, w8=None):
         """the verify forward of prompt-lookup decoding: M = x.shape[0] consecutive new positions of ONE sequence (embedding rows x [M, H], rotary positions
         pos_rows [M], key ranges krange [M, 2] = [lo, end + j), cache slots *start_dev + j) in one pass over the decoder weights -> fp32 logits [M, V].  Up to
         _chain_batch_cap rows: the batched decode chain with its cache strides aliased onto the one sequence; above (or where the chain does not apply):
-        _decode_layers on the interval kernel, then the lm_head GEMM."""
+        _decode_layers on the interval kernel, then the lm_head GEMM.  w8: the chain on the FP8 copy (generate() resolved that the k + 1 rows take it)."""
         M = x.shape[0]
         if self._lookup_chain_ok(M, head):
-            return self._decode_layers_chain_batched(x, M, cache, pos_rows, krange, start_dev, aws, head, one_sequence=True)
+            return self._decode_layers_chain_batched(x, M, cache, pos_rows, krange, start_dev, aws, head, one_sequence=True, w8=w8)
         y = self._decode_layers(x, 1, M, None, cache, pos_rows, krange.view(1, M, 2), False, start_dev=start_dev)
         return ops.gemm_nt(y, head).float()

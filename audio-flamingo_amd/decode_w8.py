@@ -3,7 +3,8 @@ one launch per Linear, csrc/decode_chain.hip) spends most of a token streaming b
 of them in OCP e4m3fn with one power-of-two fp32 scale per output row - half the bytes.  Weights only: activations, accumulation, the rounding points, the KV
 cache, the prefill and forward() stay what they are.  The copy is extra memory (the prefill GEMMs keep reading the bf16 weights), built on first use and rebuilt
 whenever arena.version() has moved.  The quantisation rule is in csrc/decode_w8.hip (contract: include/afk.h; torch restatement: tests/_w8_ref.py).
-docs/generate.md, "FP8 decode weights".
+docs/generate.md, "FP8 decode weights".  decode_weights_batched= / AFK_DECODE_WEIGHTS_BATCHED (default off) lets decode steps of 2 - 8 rows - the matrix-pipe
+launches of decode_forward._decode_layers_chain_batched - read the same copy; "FP8 decode weights, 2 - 8 rows" there.
 
   resolve(...)        pure, CPU-runnable: the keyword against the class attribute, with the refusals -> True (the FP8 route) | False (today's route)
   Q8                  one quantised tensor: codes uint8 [N, K], scale fp32 [N]
@@ -21,14 +22,20 @@ LAYER_KEYS = ("self_attn.qkv.weight", "self_attn.o_proj.weight", "mlp.gate_up.we
 
 
 def resolve(decode_weights=None, default="bf16", *, rows=1, num_beams=1, copies=1, guidance=False, lookup=False, share_prompt=None, use_cache=True,
-            exact_fp32=False, chain_ok=True, widths_ok=True, head_ok=True, assist=False):
+            exact_fp32=False, chain_ok=True, widths_ok=True, head_ok=True, assist=False, batched=False, step_rows=None, batched_ok=True):
     """decode_weights (None: `default`, the model's decode_weight_dtype) -> True where the call decodes on the FP8 copy, False for today's route ("bf16").
     Anything but None, "bf16" or "fp8" (keyword or default) is a ValueError.  FP8 runs on the single-sequence chain only; the calls that do not run it -
     decode_weights="fp8": an AfkError naming the combination; None with the default on: False, silently (the share_prompt convention):
       more than one row after input expansion (rows); num_beams > 1; num_return_sequences > 1 (copies); active guidance_scale (guidance); prompt-lookup
       decoding (lookup); assisted decoding (assist: assistant_model=); share_prompt=True; use_cache=False; AFK_EXACT_FP32=1 (exact_fp32); a geometry
       outside the single-sequence chain (chain_ok False); hidden size, Hq * head_dim or intermediate size not a multiple of 16 (widths_ok False); lm_head
-      rows not a multiple of 8 (head_ok False)."""
+      rows not a multiple of 8 (head_ok False).
+    batched (decode_weights_batched= / the class attribute / AFK_DECODE_WEIGHTS_BATCHED; off: nothing above changes): a call whose decode step has 2 - 8 rows -
+    a batch of prompts, num_return_sequences copies, beams, an active guidance_scale, prompt-lookup decoding, share_prompt=True - decodes on the FP8 copy through
+    the matrix-pipe launches of the batched chain (afk_decode_chain_*_batched_w8) -> True.  step_rows: the rows of a decode step (None: rows * num_beams, twice
+    that under guidance; prompt-lookup decoding: k + 1).  Refused there, by name under the keyword and silently under the default: more than 8 rows in a step,
+    assistant_model=, use_cache=False, AFK_EXACT_FP32=1, a step that does not run the norm-in-prologue launches (batched_ok False: decode_norm_mode, the row
+    bounds decode_mfma_from .. decode_prologue_max, the geometry).  A call of one row keeps the rules above whatever `batched` says."""
     from ._lib import AfkError
 
     for what, v in (("decode_weights", decode_weights), ("decode_weight_dtype", default)):
@@ -36,6 +43,17 @@ def resolve(decode_weights=None, default="bf16", *, rows=1, num_beams=1, copies=
             raise ValueError(f"`{what}` has to be None, 'bf16' or 'fp8', but is {v!r}")
     if (default if decode_weights is None else decode_weights) != "fp8":
         return False
+    n = int(step_rows) if step_rows is not None else int(rows) * max(int(num_beams), 1) * (2 if guidance else 1)
+    if batched and n >= 2:
+        bad = [what for on, what in ((n > 8, f"{n} rows in a decode step (more than 8)"), (bool(assist), "assistant_model="), (not use_cache, "use_cache=False"),
+                                     (bool(exact_fp32), "AFK_EXACT_FP32=1"),
+                                     (not batched_ok and n <= 8, "a decode step outside the norm-in-prologue launches of the batched decode chain")) if on]
+        if bad:
+            if decode_weights is None:
+                return False
+            raise AfkError(f"generate(decode_weights='fp8', decode_weights_batched=True) with {' / '.join(bad)}: the batched FP8 launches take 2 - 8 rows "
+                           f"of the matrix-pipe decode chain, on the KV cache")
+        return True
     bad = [what for on, what in ((int(rows) > 1, "more than one row"), (int(num_beams) > 1, "num_beams > 1"), (int(copies) > 1, "num_return_sequences > 1"),
                                  (bool(guidance), "guidance_scale="), (bool(lookup), "prompt_lookup_num_tokens="), (bool(assist), "assistant_model="),
                                  (share_prompt is True, "share_prompt=True"), (not use_cache, "use_cache=False"), (bool(exact_fp32), "AFK_EXACT_FP32=1"),

@@ -60,7 +60,7 @@ class DecodeState:
     single: Optional[SingleSequence] = None
     on_device: Optional[OnDevice] = None
     shared: Optional[_share.SharedPrompt] = None   # the prompt cache of a call that shares it (decode_share.py): `cache` is then the TAIL cache, cur counts its slots from 0
-    w8: Optional[_w8mod.DecodeW8] = None   # FP8 decode weights (decode_w8.py): the single-sequence chain streams this copy of its Linears and of the lm_head
+    w8: Optional[_w8mod.DecodeW8] = None   # FP8 decode weights (decode_w8.py): the single-sequence chain - with decode_weights_batched the 2 - 8-row chain too - streams this copy of its Linears and of the lm_head
     cfg: Optional[_cfg.CfgState] = None   # classifier-free guidance (decode_cfg.py): cache, lo and nxt have 2 * B rows - [0, B) conditional, [B, 2B) unconditional - and everything else B
 
 
@@ -253,7 +253,7 @@ class AfkGenerationMixin:
 
     # ------------------------------------------------------------------ beam search
     @torch.no_grad()
-    def _beam_search(self, ids, last_hidden, cache, lo, nb, max_new, eos, pad, length_penalty, early_stopping, *, num_return=1, use_graph=None, share=None):
+    def _beam_search(self, ids, last_hidden, cache, lo, nb, max_new, eos, pad, length_penalty, early_stopping, *, num_return=1, use_graph=None, share=None, w8=None):
         """Beam search on the KV cache with GenerationMixin's scoring (transformers/generation/utils.py:3008-3400): every batch row keeps `nb`
         running beams ranked by accumulated log-probability; at each step the best (n_eos + 1) * nb continuations over all beams are drawn, the
         ones among the top nb that end (EOS, or the length limit) compete for the row's nb FINISHED slots with score = sum / generated_length ^
@@ -271,14 +271,14 @@ class AfkGenerationMixin:
         V = self.V
         if share is not None:   # the prompt cache is the prefill's own (no headroom, no per-beam copy); the beams' generated positions live in a tail cache
             shared, tail, lo_rep, rep = self._share_setup(share, cache, lo, S0, max_new)
-            return self._beam_search_device(ids, last_hidden, tail, lo_rep, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph, shared=shared)
+            return self._beam_search_device(ids, last_hidden, tail, lo_rep, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph, shared=shared, w8=w8)
         rep = torch.arange(B, device=dev).repeat_interleave(nb)   # one cache row per beam
         Kc, Vt = cache[0].index_select(1, rep).contiguous(), cache[1].index_select(1, rep).contiguous()
         lo = lo.index_select(0, rep).contiguous()
         if self.beam_on_device and not _exact.ENABLED and ops.beam_caps_ok(nb, len(eos), V):
-            return self._beam_search_device(ids, last_hidden, (Kc, Vt), lo, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph)
+            return self._beam_search_device(ids, last_hidden, (Kc, Vt), lo, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph, w8=w8)
         keep = (len(eos) + 1) * nb
-        st = self._new_state((Kc, Vt), lo, S0, torch.zeros(B * nb, device=dev, dtype=torch.int64))
+        st = self._new_state((Kc, Vt), lo, S0, torch.zeros(B * nb, device=dev, dtype=torch.int64), w8=w8)
         run_seq = torch.zeros((B, nb, max_new), device=dev, dtype=torch.int64)
         run_score = torch.full((B, nb), -1.0e9, device=dev, dtype=torch.float32)
         run_score[:, 0] = 0.0                                           # all beams of a row start identical: only the first one is live
@@ -340,7 +340,7 @@ class AfkGenerationMixin:
         return torch.cat([ids.repeat_interleave(n, dim=0) if n > 1 else ids, best_seq[:, : int(best_len.max())]], dim=1)
 
     @torch.no_grad()
-    def _beam_search_device(self, ids, last_hidden, cache, lo, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph, shared=None):
+    def _beam_search_device(self, ids, last_hidden, cache, lo, rep, nb, max_new, eos, pad, length_penalty, early_stopping, num_return, use_graph, shared=None, w8=None):
         """_beam_search with every per-token decision on the device (cache, lo: one row per beam, rep: each one's prompt row).  A step is _decode_logits -> afk_beam_step (log-softmax, the row's top (n_eos + 1) * nb
         continuations, finished slots, running beams, the early-stop heuristic, {t, open} in a status word) -> afk_beam_reorder_cache (the slots written since
         the prompt move by parentage, in place: the beams of a row share their prompt keys bit for bit) -> cur += 1; nothing in it depends on the host, so it is
@@ -353,7 +353,7 @@ class AfkGenerationMixin:
         bs = ops.beam_state(B, nb, max_new, device=self.device_, eos=eos, length_penalty=length_penalty, early_stopping=early_stopping)
         if shared is not None:
             S0 = 0   # of the cache the step appends to
-        st = self._new_state(cache, lo, S0, bs["next_token"], shared=shared)
+        st = self._new_state(cache, lo, S0, bs["next_token"], shared=shared, w8=w8)
         ops.beam_step(ops.gemm_nt(last_hidden, st.head).float().index_select(0, rep).contiguous(), bs, step_off=0)
 
         def step():   # token t = cur + 1 - S0: the forward pass appends the keys of token t - 1 at slot cur, so the slots S0 .. cur move
@@ -375,7 +375,7 @@ class AfkGenerationMixin:
                  epsilon_cutoff=0.0, eta_cutoff=0.0, num_return_sequences=None, sequence_bias=None, bad_words_ids=None, min_length=0,
                  forced_eos_token_id=None, exponential_decay_length_penalty=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, share_prompt=None,
                  guidance_scale=None, negative_prompt_ids=None, negative_prompt_attention_mask=None, decode_weights=None, assistant_model=None,
-                 num_assistant_tokens=None, **kwargs):
+                 num_assistant_tokens=None, decode_weights_batched=None, **kwargs):
         """Greedy decoding, sampling or beam search on a KV cache, with GenerationMixin.generate's arguments and results; docs/generate.md describes every
         route, what it launches and how it differs from the reference.
 
@@ -416,6 +416,10 @@ class AfkGenerationMixin:
         an FP8 copy of the decoder Linears and the lm_head (OCP e4m3fn codes, one power-of-two scale per output row: half the bytes; decode_w8.py), built on
         first use and rebuilt when the weights have changed.  Weights only: the prefill, the activations and the cache are what they are, and the decode logits
         differ from the bf16 route by the quantisation.  "bf16": not one launch or allocation differs.  docs/generate.md, "FP8 decode weights".
+        decode_weights_batched (None: the class attribute decode_weights_batched, env AFK_DECODE_WEIGHTS_BATCHED, default off) with decode_weights "fp8": decode
+        steps of 2 - 8 rows - a batch of prompts, num_return_sequences copies, beams, an active guidance_scale, the verify pass of prompt-lookup decoding,
+        share_prompt=True - read the same FP8 copy through the matrix-pipe launches of the batched chain (afk_decode_chain_*_batched_w8).  Off: not one launch,
+        allocation, refusal or result differs; one row decodes as decode_weights alone says.  docs/generate.md, "FP8 decode weights, 2 - 8 rows".
         assistant_model (None) with num_assistant_tokens (k; None: the assistant's generation_config.num_assistant_tokens, else 5): assisted (speculative)
         decoding - a second, smaller model of this package with the same vocabulary drafts k tokens per step on a cache of its own (prefilled with the same
         prompt and audio), this model verifies them in one pass over its weights and emits the confirmed ones plus one; the ids are the plain greedy ids.  The
@@ -442,7 +446,9 @@ class AfkGenerationMixin:
         past_key_values or share_prompt=True, with a negative prompt that holds the audio id or a negative mask that is not left padding (AfkError), with
         negative_prompt_ids of another batch size or a mask of another shape (ValueError) (decode_cfg.resolve); decode_weights="fp8" with more than one
         row, num_beams > 1, num_return_sequences > 1, guidance_scale, prompt-lookup decoding, share_prompt=True, use_cache=False, AFK_EXACT_FP32=1 or a
-        geometry the single-sequence chain or its FP8 launches do not take (AfkError), any other value (ValueError) (decode_w8.resolve)."""
+        geometry the single-sequence chain or its FP8 launches do not take (AfkError), any other value (ValueError); with decode_weights_batched: more than
+        8 rows in a decode step, assistant_model=, use_cache=False, AFK_EXACT_FP32=1 or a step outside the norm-in-prologue launches (AfkError)
+        (decode_w8.resolve)."""
         self._require_hip()
         self.last_share_stats = self.last_cfg_stats = self.last_w8_stats = self.last_assist_stats = None
         procs, criteria, streamer = kwargs.pop("logits_processor", None), kwargs.pop("stopping_criteria", None), kwargs.pop("streamer", None)
@@ -509,7 +515,8 @@ class AfkGenerationMixin:
                                     assist=assist is not None)
         # FP8 decode weights: keyword, else the class attribute; False: today's route, and nothing below changes
         fp8 = self._w8_resolve(decode_weights, input_ids.shape[0] * (n_ret if int(num_beams) == 1 else 1), int(num_beams), n_ret, cfg is not None, lookup is not None,
-                               share_prompt, bool(use_cache), _exact.ENABLED, assist=assist is not None)
+                               share_prompt, bool(use_cache), _exact.ENABLED, assist=assist is not None, batched=decode_weights_batched,
+                               lookup_rows=lookup.k + 1 if lookup is not None else None)
         if spec.active and (num_beams > 1 or not use_cache):
             raise AfkError("generate(repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / begin_suppress_tokens / sequence_bias / "
                            "bad_words_ids / min_length / forced_eos_token_id / exponential_decay_length_penalty): greedy or sampled decoding on the KV cache "
@@ -562,7 +569,8 @@ class AfkGenerationMixin:
 
                 cont = (cont[0], AfkKVCache(Kc, Vt, lo, 0), 0)
         if num_beams > 1:
-            return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), max_new, eos, pad, float(length_penalty), early_stopping, num_return=n_ret, use_graph=use_graph, share=share)
+            return self._beam_search(ids, last, (Kc, Vt), lo, int(num_beams), max_new, eos, pad, float(length_penalty), early_stopping, num_return=n_ret, use_graph=use_graph, share=share,
+                                     w8=self._w8_current() if fp8 else None)
         first_logits = ops.gemm_nt(last, self.arena["lm_head.weight"].data).float()
         V = first_logits.shape[1]
         shared = None
@@ -577,7 +585,8 @@ class AfkGenerationMixin:
             # 2 * B rows, aligned to the right at slot Smax; from here on lo has 2 * B entries and the steps append at Smax, Smax + 1, ...
             guide, (Kc, Vt), lo, uncond_first = self._cfg_setup(cfg, ids, (Kc, Vt), lo, S0, max_new, V)
         if lookup is not None:
-            return self._continue_done(cont, self._generate_lookup(ids, first_logits, (Kc, Vt), lo, lookup, max_new, eos, use_graph))
+            return self._continue_done(cont, self._generate_lookup(ids, first_logits, (Kc, Vt), lo, lookup, max_new, eos, use_graph,
+                                                                  w8=self._w8_current() if fp8 else None))
         if assist is not None:
             return self._generate_assisted(ids, input_features, input_features_mask, attention_mask, first_logits, (Kc, Vt), lo, assist, max_new, eos, use_graph)
         rec = None
@@ -715,7 +724,7 @@ class AfkGenerationMixin:
         return result
 
     @torch.no_grad()
-    def _generate_lookup(self, ids, first_logits, cache, lo, lookup, max_new, eos, use_graph):
+    def _generate_lookup(self, ids, first_logits, cache, lo, lookup, max_new, eos, use_graph, w8=None):
         """greedy decoding of one sequence by prompt lookup (decode_lookup.py): token 0 is the argmax of the prefill's logits; from then on a step is
         afk_lookup_draft (up to k candidates from the ids so far + the k + 1 input rows) -> _lookup_forward (one pass over the weights, the rows appended at the
         cache slots cur .. cur + k) -> afk_lookup_accept (row argmaxes, the confirmed prefix + one token, ids / tokens / status / [end, cur, position] advanced by
@@ -736,7 +745,7 @@ class AfkGenerationMixin:
 
         def step():
             draft(ls, emb)
-            accept(ls, self._lookup_forward(ls["x"], cache, ls["pos"], ls["krange"], state[2:3], aws, head))
+            accept(ls, self._lookup_forward(ls["x"], cache, ls["pos"], ls["krange"], state[2:3], aws, head, w8=w8))
 
         done = lambda t=0: ls["status"].tolist()[_lookup.DONE] != 0   # one small copy
         launched = 0

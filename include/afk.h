@@ -720,6 +720,22 @@ int afk_decode_chain_lm_head_norm_batched(const void* x, int64_t ldx, int M, con
  * 1 <= M <= 32; ss_part holds G x 8 x (N / 16) floats, G = the groups of eight sequences the launch RUNS: 1 (M <= 8), 2 (M <= 16) or 4 (an empty group writes zeros). */
 int afk_decode_chain_linear_residual_ss_batched(const void* x, int64_t ldx, int M, const void* W, int64_t ldw, int N, int K, const void* residual, int64_t ld_res,
                                                 void* out, int64_t ld_out, float* ss_part, void* stream);
+/* FP8 decode weights for 1 .. 8 sequences (generate(decode_weights="fp8", decode_weights_batched=True)): the four matrix-pipe launches of the default 2 - 8-row step
+ * with W, ldw replaced by Wq, ld_wq, wscale - row r of the Linear is wscale[r] * code[r][:], the contract of afk_quantize_rows_fp8 (OCP e4m3fn codes).  A wave loads 16
+ * codes per lane, widens them to bf16 (exact; v_cvt_scalef32_pk_bf16_fp8 with scale 1) in front of the LDS park and multiplies them on v_mfma_f32_32x32x16_bf16: the K
+ * partition, the fp32 accumulation, the prologue, the ss_part hand-over and every rounding point are the bf16 twin's; wscale[r] multiplies the finished fp32 sum in front
+ * of the bias add and the first bf16 rounding.  No byte behind column K of a row is read.  1 <= M <= 8 (more rows are refused), ld_wq >= K, ld_wq % 16 == 0, Wq 16-byte
+ * aligned, wscale non-null; otherwise the twin's conditions (K % 64 == 0). */
+int afk_decode_chain_qkv_norm_batched_w8(const void* x, int64_t ldx, int M, const void* norm_w, float eps, const void* Wq, int64_t ld_wq, const float* wscale, int K,
+                                         const void* bias, const void* cos_t, const void* sin_t, const int* pos, void* q_out, int64_t ldq, void* kcache, int64_t k_bs,
+                                         void* vtcache, int64_t vt_bs, int spad, const int* start_dev, int Hq, int Hkv, int D, const float* ss_part, int ss_nparts,
+                                         void* stream);
+int afk_decode_chain_gate_up_norm_batched_w8(const void* x, int64_t ldx, int M, const void* norm_w, float eps, const void* Wq, int64_t ld_wq, const float* wscale, int I,
+                                             int K, void* act_out, int64_t ld_act, const float* ss_part, int ss_nparts, void* stream);
+int afk_decode_chain_lm_head_norm_batched_w8(const void* x, int64_t ldx, int M, const void* norm_w, float eps, const void* Wq, int64_t ld_wq, const float* wscale, int N,
+                                             int K, float* logits, int64_t ld_logits, const float* ss_part, int ss_nparts, void* stream);
+int afk_decode_chain_linear_residual_ss_batched_w8(const void* x, int64_t ldx, int M, const void* Wq, int64_t ld_wq, const float* wscale, int N, int K,
+                                                   const void* residual, int64_t ld_res, void* out, int64_t ld_out, float* ss_part, void* stream);
 /* Linear + residual + the RMSNorm that follows it in ONE launch, 1 .. 8 sequences (round 6): out = bf16(W x) + residual (Qwen2DecoderLayer :284 / :297), h_out =
  * RMSNorm(out) with norm_w (the layer's post_attention_layernorm :294, the NEXT layer's input_layernorm :271, or Qwen2Model.norm; Qwen2RMSNorm :247-252: cast before
  * the weight multiply).  The statistic needs every output column: the last block of the launch to arrive normalises (hand-over through agent-scope stores and a
