@@ -1302,10 +1302,34 @@ def loss_reduce(row_loss, denom, loss, *, accumulate=False):
 
 
 # ---------------------------------------------------------------------------------------------- optimizer
+def _chk_adamw32(who, master, m, v, grad, param, numel, shadow=None, NK=None):
+    """the five streams of the fp32-state AdamW launches: fp32 master / m / v, bf16 grad / param, contiguous, `numel` elements each, and (transposed
+    form) a bf16 shadow that can hold [K, N]; all on the device.  The kernels index the five streams by one offset: a short or a wrongly typed
+    buffer would be read and written out of bounds."""
+    streams = ((master, torch.float32, "master"), (m, torch.float32, "m"), (v, torch.float32, "v"), (grad, BF16, "grad"), (param, BF16, "param"))
+    for t, dtype, what in streams:
+        if t.dtype != dtype:
+            raise AfkError(f"{who} {what}: expected dtype {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise AfkError(f"{who} {what}: not contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+        if t.numel() != numel:
+            raise AfkError(f"{who} {what}: {t.numel()} elements, expected {numel}")
+    if shadow is not None:
+        N, K = NK
+        if shadow.dtype != BF16:
+            raise AfkError(f"{who} shadow: expected dtype {BF16}, got {shadow.dtype}")
+        if shadow.dim() != 2 or shadow.stride(1) != 1 or shadow.shape[0] < K or shadow.shape[1] < N or shadow.stride(0) < N:
+            raise AfkError(f"{who} shadow: {tuple(shadow.shape)} (strides {shadow.stride()}) cannot hold [K, N] = [{K}, {N}]")
+        streams += ((shadow, BF16, "shadow"),)
+    for t, _, what in streams:
+        _chk(t, None, f"{who} {what}")
+
+
 def adamw_step(master, m, v, grad, param, *, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, max_blocks=0, gate=None, hyper=None):
     """gate: optional device int32[1]; the launch leaves every buffer untouched when it reads 0.
     hyper: optional device float32[4] = (lr, 1 - beta1^t, sqrt(1 - beta2^t), gradient multiplier) overriding lr / step (HIP-graph replay);
     hyper[3] multiplies every gradient (global-norm clip coefficient, 1 = off)"""
+    _chk_adamw32("adamw", master, m, v, grad, param, param.numel())
     _lib.call("afk_adamw_step", master.data_ptr(), m.data_ptr(), v.data_ptr(), grad.data_ptr(), param.data_ptr(), param.numel(),
               float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step), float(grad_scale),
               int(max_blocks), _p(gate), _p(hyper), _stream())
@@ -1313,6 +1337,7 @@ def adamw_step(master, m, v, grad, param, *, lr, beta1, beta2, eps, weight_decay
 
 def adamw_step_t(master, m, v, grad, param, shadow, N, K, *, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, max_blocks=0, gate=None, hyper=None):
     """afk_adamw_step on one 2-D weight [N, K] (flat views of the arena) that also writes shadow [K, ld] = the K-major copy of the updated weight"""
+    _chk_adamw32("adamw_t", master, m, v, grad, param, int(N) * int(K), shadow, (int(N), int(K)))
     _lib.call("afk_adamw_step_t", master.data_ptr(), m.data_ptr(), v.data_ptr(), grad.data_ptr(), param.data_ptr(), shadow.data_ptr(), int(N), int(K),
               shadow.stride(0), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step), float(grad_scale), int(max_blocks),
               _p(gate), _p(hyper), _stream())
